@@ -8,12 +8,18 @@ f32 pooled tail) - 256 utterances per GPU per step, exactly as configs[1] states
 Weak scaling: every rank extracts its own shard; with N > 1 the embeddings are collected with one RCCL all-gather per
 step (the path's only exchange).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 without a launcher: bench.py spawns its own ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                               (N > 1 without a launcher: bench.py spawns its own ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement): `value` from the MEDIAN of `repeats` back-to-back
-timed regions of exactly K steps each (one region is ~16 ms: the regions are repeated until >= 1 s has been measured),
-`roofline` (frame-level GEMM launches, hipEvent-timed inside libasv_amd.so on the extract stream during timed steps),
+A plain run sets up, settles the clock, runs W warm-up steps, times ONE region of exactly K steps and prints ONE JSON line
+on rank 0: `value` = utterances per second of that region, `ms_per_step` = its time / K.  `--dump-outputs DIR` writes
+what the last timed step delivered to its caller (the embeddings; gathered over the ranks when N > 1) to DIR/embeddings.npy
+(float32); the inputs and weights are seeded, so the same arguments give the same inputs in every run.
+
+`--full` adds everything else, as described below.  With it, `value` comes from the MEDIAN of `repeats` back-to-back
+timed regions of exactly K steps each (the regions are repeated until >= --min-seconds have been measured), and the line
+adds `roofline` (frame-level GEMM launches, hipEvent-timed inside libasv_amd.so on the extract stream during timed steps),
 `parity` (utterances of the timed batch against the CPU port of the reference + the north star's two gates: embeddings
 within 1e-4, EER delta < 0.01 % on a 50 000-trial planted-speaker set against the exact-f32 extraction), `cpu_baseline`
 (N = 1 only) and, at N = 1, `supplementary` records: the same workload in the f16 / f32x / f32 precision modes (each with
@@ -61,6 +67,7 @@ DOMINANT_NAMES = {"xvector": "tdnn_chain_kernel / tdnn_chainx_kernel:", "ecapa":
 
 
 LINE_TARGET, LINE_LIMIT = 4096, 8000      # bytes of the final stdout line: the driver parses that line, and a 19 KB one was not held (BENCH_r05)
+DUMP_LIMIT = 64 << 20                     # bytes of --dump-outputs at most
 
 
 def compact_record(res):
@@ -157,6 +164,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the embeddings of the last timed step (float32) to DIR/embeddings.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: repeated timed regions (--min-seconds), hipEvent roofline, "
+                         "single-stream pass, HBM traffic, parity and EER gates, supplementary models / modes, parity_grade, cpu_baseline, "
+                         "verification of the all-gather")
     ap.add_argument("--precision", default="bf16", help="bf16 (default, BASELINE configs[1]) | f16 | f32x[-bf16|-f16] | f32")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL on the GPUs (default); gloo needs --dry-run")
     ap.add_argument("--dry-run", action="store_true",
@@ -454,9 +467,12 @@ def main():
         for _ in range(warmup):
             step()
         barrier()
-        # one probe region decides how many regions make up min_seconds (the same number on every rank)
-        probe = timed(steps)
-        repeats = max(3, int(min_seconds / max(probe, 1e-6)) + 1)
+        if args.full:
+            # one probe region decides how many regions make up min_seconds (the same number on every rank)
+            probe = timed(steps)
+            repeats = max(3, int(min_seconds / max(probe, 1e-6)) + 1)
+        else:
+            repeats = 1                                                 # a plain run times exactly `steps` steps
         stride = max(1, args.event_stride)
         rows = []
         if profile:
@@ -475,14 +491,16 @@ def main():
             if sampled:
                 rows.extend(eng.get_profile())
         eng.set_profiling(False)
+        # what the caller of the last timed step received (later profiled steps reuse the buffers)
+        output = (gathered if collective else outs)[(counter[0] - 1) % nbuf].clone()
         gather_ok = None
-        if dry and collective:
+        if args.full and dry and collective:
             # the dry run also checks WHAT the double-buffered gather delivered: every rank's block of the last two steps
             # against that rank's stand-in result, recomputed here from its seed
             barrier()
             want = torch.cat([DryRunWorkload(args, B, wl.T, r).eng.extract_device(DryRunWorkload(args, B, wl.T, r).feats, wl.offsets) for r in range(world)])
             gather_ok = all(bool(torch.equal(g, want)) for g in gathered)
-        elif collective:
+        elif args.full and collective:
             # on the device: this rank's block of what the last all-gathers delivered equals its own embeddings, bit for bit
             barrier()
             gather_ok = all(bool(torch.equal(gathered[k][rank * B:(rank + 1) * B], outs[k])) for k in range(nbuf) if counter[0] > k)
@@ -490,7 +508,7 @@ def main():
         med = allr[len(allr) // 2]
         rec = {"value": round(world * B * steps / med, 1), "ms_per_step": round(1e3 * med / steps, 4), "repeats": len(allr),
                "timed_seconds": round(sum(allr), 3),
-               "ms_per_step_min_max": [round(1e3 * allr[0] / steps, 4), round(1e3 * allr[-1] / steps, 4)]}
+               "ms_per_step_min_max": [round(1e3 * allr[0] / steps, 4), round(1e3 * allr[-1] / steps, 4)], "output": output}
         if gather_ok is not None:
             rec["gather_verified"] = gather_ok
         if dts and dts_sampled:
@@ -646,9 +664,16 @@ def main():
         one_only = ("f32",) if args.batch <= 320 else ("f32x", "f32m", "f32")
         args.streams = 2 if (not dry and not args.from_wav and not args.per_op and args.precision.split("-")[0] not in one_only) else 1
     wl2 = [Workload(args, args.model, args.precision, args.batch, args.frames, rank, dev, lengths=lengths) for _ in range(args.streams - 1)] if (args.streams >= 2 and not dry) else None
-    head = measure(wl, args.steps, args.warmup, args.min_seconds, not args.no_profile and not dry and wl2 is None, dist_on, per_op=args.per_op, from_wav=args.from_wav, wl2=wl2)
+    head = measure(wl, args.steps, args.warmup, args.min_seconds, args.full and not args.no_profile and not dry and wl2 is None, dist_on, per_op=args.per_op,
+                   from_wav=args.from_wav, wl2=wl2)
+    if args.dump_outputs and rank == 0:
+        emb = head["output"].cpu().numpy().astype(np.float32)
+        if emb.nbytes > DUMP_LIMIT:                                      # a fixed subset of rows: the same in every run
+            emb = emb[np.linspace(0, len(emb) - 1, DUMP_LIMIT // emb[0].nbytes).astype(np.int64)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "embeddings.npy"), emb)
     single = None
-    if wl2 is not None:
+    if wl2 is not None and args.full:
         # the kernel-level figures (roofline: hipEvents around the GEMM launches of ONE stream) come from a single-stream pass
         single = measure(wl, args.steps, 2, min(args.min_seconds, 0.6), not args.no_profile, dist_on)
         if "roofline" in single:
@@ -714,10 +739,10 @@ def main():
                                                          ", batch of that collection: " + str(info.get("batch", 640)) + ")", "live_pass": detail}
 
     modes = {}
-    if rank == 0 and args.model == "xvector" and not dry and not args.lengths:
+    if args.full and rank == 0 and args.model == "xvector" and not dry and not args.lengths:
         res["parity"] = gates_of(wl) if (world == 1 and not args.from_wav) else parity_of(wl)
         modes[args.precision] = {"value": head["value"], "gate_1e-4": res["parity"]["gate_1e-4"], "eer_gate": res["parity"].get("eer_gate")}
-    if rank == 0 and world == 1 and not args.no_supplementary and args.model == "xvector" and not args.from_wav and not dry and not args.lengths:
+    if args.full and rank == 0 and world == 1 and not args.no_supplementary and args.model == "xvector" and not args.from_wav and not dry and not args.lengths:
         # ---- supplementary records, same harness (shorter: 0.4 s of timed regions each) --------------
         sup = {}
         two = args.streams >= 2
@@ -832,7 +857,7 @@ def main():
                                              "1e-4 and EER delta < 0.01 % on every draw of parity_grade.xvector")
             res["value_eer_grade"] = dict(xv["fastest_mode_passing_eer_gate_on_every_draw"], rule="the fastest mode inside the EER gate on every draw, whatever its embedding error")
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and not dry and not args.lengths:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and not dry and not args.lengths:
         from oracle import torch_cpu_port as P                        # cpu_baseline leg only
         # torch's default (one thread per core) collapses on many-core hosts for these small
         # convolutions: probe a few thread counts briefly and time the sample with the best one

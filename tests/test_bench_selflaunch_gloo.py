@@ -17,7 +17,7 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 def _run(gpus, launcher):
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--backend", "gloo", "--dry-run", "--steps", "6", "--warmup", "2",
-           "--batch", "48", "--frames", "50", "--min-seconds", "0.05", "--settle-seconds", "0.02"]
+           "--batch", "48", "--frames", "50", "--min-seconds", "0.05", "--settle-seconds", "0.02", "--full"]
     if launcher:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1", "--master-port", "29731"] + cmd[1:]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
@@ -41,6 +41,33 @@ def test_bench_dry_run_control_flow(gpus, launcher):
     assert abs(rec["value"] - gpus * 48 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 0.01        # value = whole-job units / time
     if gpus > 1:
         assert rec["gather_verified"] is True and rec["backend"] == "gloo"
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_run_times_exactly_k_steps_and_dumps_the_last_output(gpus, tmp_path):
+    """Without --full the run times ONE region of exactly --steps steps, and --dump-outputs writes what the last timed step
+    delivered to its caller (the gathered embeddings when N > 1): the same array in every run with the same arguments."""
+    import argparse
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        out = tmp_path / str(i)
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--backend", "gloo", "--dry-run", "--steps", "5", "--warmup", "1",
+               "--batch", "48", "--frames", "50", "--settle-seconds", "0.02", "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+        assert res.returncode == 0, res.stdout + res.stderr
+        rec = json.loads(res.stdout.rstrip("\n").splitlines()[-1])
+        assert rec["steps"] == 5 and rec["ms_per_step"] > 0 and "gather_verified" not in rec
+        full = json.loads([l for l in res.stderr.splitlines() if l.startswith("bench.py full record: ")][-1].split(": ", 1)[1])
+        assert full["timing"]["regions"] == 1 and full["timing"]["steps_per_region"] == 5
+        dumps.append(np.load(out / "embeddings.npy"))
+    args = argparse.Namespace(feat_dim=80)
+    want = np.concatenate([w.eng.extract_device(w.feats, w.offsets).numpy() for w in (bench.DryRunWorkload(args, 48, 50, r) for r in range(gpus))])
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (gpus * 48, bench.DryRunEngine.embed_dim)
+    assert np.array_equal(dumps[0], want) and np.array_equal(dumps[1], want)
 
 
 def test_bench_refuses_gloo_without_dry_run():

@@ -106,7 +106,7 @@ def test_sharded_script_under_the_launcher_collects_through_rccl(tmp_path):
 def test_bench_under_the_launcher_gathers_through_rccl():
     bench = os.path.join(helpers.REPO, "bench.py")
     res = subprocess.run(_launcher(_free_port()) + [bench, "--gpus", "1", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--settle-seconds", "0.1",
-                                                    "--no-supplementary", "--cpu-seconds", "0", "--eer-trials", "0", "--no-profile", "--batch", "64"],
+                                                    "--no-supplementary", "--cpu-seconds", "0", "--eer-trials", "0", "--no-profile", "--batch", "64", "--full"],
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]

@@ -263,59 +263,34 @@ def test_pipe_writer_waits_for_the_child_and_reports_its_status(tmp_path):
         bad.close()
 
 
-REF_KALDI_IO = "/root/reference/pytorch/libs/support/kaldi_io.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_KALDI_IO), reason="reference tree only exists in the build container")
-def test_wire_format_against_the_reference_kaldi_io(tmp_path):
-    """pin libs.support.kaldi_io to the reference's own vendored module (kaldi_io.py:329-608), in a
-    subprocess that imports it from /root/reference: bytes written by either side are equal, and each side reads what
-    the other wrote - float / double matrices and vectors, text matrices, and the 'CM ' decode."""
-    import subprocess
-    import sys
+def wire_format_inputs():
+    """The seeded inputs of the wire-format check (oracle/gen_reference_checks_golden.py feeds the same ones to the reference)."""
     rng = np.random.RandomState(7)
     cols = 5
     pct = np.sort(rng.randint(0, 65536, size=(cols, 4)), axis=1)
-    cm = _cm_entry("cm", rng.randint(0, 256, size=(cols, 33)), pct, -1.5, 4.25)
-    (tmp_path / "cm.ark").write_bytes(cm)
-    (tmp_path / "txt.ark").write_bytes(b"tx  [\n  1.5 -2 3\n  4 5 6.25 ]\n")
-    np.save(tmp_path / "m32.npy", rng.randn(9, 4).astype(np.float32))
-    np.save(tmp_path / "m64.npy", rng.randn(3, 7))
-    np.save(tmp_path / "v32.npy", rng.randn(192).astype(np.float32))
-    code = r'''
-import sys, os, importlib.util, numpy as np
-sys.dont_write_bytecode = True
-spec = importlib.util.spec_from_file_location("ref_kaldi_io", %(ref)r)
-R = importlib.util.module_from_spec(spec); spec.loader.exec_module(R)
-d = %(d)r
-m32, m64, v32 = np.load(d + "/m32.npy"), np.load(d + "/m64.npy"), np.load(d + "/v32.npy")
-with open(d + "/ref_out.ark", "wb") as f:
-    R.write_mat(f, m32, key="a"); R.write_mat(f, m64, key="b"); R.write_vec_flt(f, v32, key="v")
-np.save(d + "/ref_cm.npy", dict(R.read_mat_ark(d + "/cm.ark"))["cm"])
-np.save(d + "/ref_txt.npy", dict(R.read_mat_ark(d + "/txt.ark"))["tx"])
-# the reference reads what this repo wrote
-got = {}
-with open(d + "/mine_out.ark", "rb") as f:
-    k = R.read_key(f); got[k] = R.read_mat(f)
-    k = R.read_key(f); got[k] = R.read_mat(f)
-    k = R.read_key(f); got[k] = R.read_vec_flt(f)
-assert np.array_equal(got["a"], m32) and np.array_equal(got["b"], m64) and np.array_equal(got["v"], v32)
-print("REF-OK")
-''' % dict(ref=REF_KALDI_IO, d=str(tmp_path))
-    m32, m64, v32 = np.load(tmp_path / "m32.npy"), np.load(tmp_path / "m64.npy"), np.load(tmp_path / "v32.npy")
+    return dict(cm=_cm_entry("cm", rng.randint(0, 256, size=(cols, 33)), pct, -1.5, 4.25), txt=b"tx  [\n  1.5 -2 3\n  4 5 6.25 ]\n",
+                m32=rng.randn(9, 4).astype(np.float32), m64=rng.randn(3, 7), v32=rng.randn(192).astype(np.float32))
+
+
+def test_wire_format_against_the_reference_kaldi_io(tmp_path):
+    """pin libs.support.kaldi_io to the reference's own vendored module (kaldi_io.py:329-608) through
+    tests/golden/kaldi_io_reference.npz (oracle/gen_reference_checks_golden.py, which also checks that the reference reads what
+    this repository writes): bytes written by either side are equal - float / double matrices and vectors -, and so are text
+    matrices and the 'CM ' decode."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kaldi_io_reference.npz"))
+    x = wire_format_inputs()
+    (tmp_path / "cm.ark").write_bytes(x["cm"])
+    (tmp_path / "txt.ark").write_bytes(x["txt"])
     with open(tmp_path / "mine_out.ark", "wb") as f:
-        kaldi_io.write_mat(f, m32, key="a"); kaldi_io.write_mat(f, m64, key="b"); kaldi_io.write_vec_flt(f, v32, key="v")
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONPYCACHEPREFIX="/tmp/pyc_ref")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert out.returncode == 0 and "REF-OK" in out.stdout, out.stdout + out.stderr
-    assert (tmp_path / "ref_out.ark").read_bytes() == (tmp_path / "mine_out.ark").read_bytes()         # bytes equal
-    assert np.array_equal(dict(kaldi_io.read_mat_ark(str(tmp_path / "cm.ark")))["cm"], np.load(tmp_path / "ref_cm.npy"))   # 'CM ' decode equal
-    assert np.array_equal(dict(kaldi_io.read_mat_ark(str(tmp_path / "txt.ark")))["tx"], np.load(tmp_path / "ref_txt.npy"))
+        kaldi_io.write_mat(f, x["m32"], key="a"); kaldi_io.write_mat(f, x["m64"], key="b"); kaldi_io.write_vec_flt(f, x["v32"], key="v")
+    assert g["ref_out"].tobytes() == (tmp_path / "mine_out.ark").read_bytes()                                  # bytes equal
+    assert np.array_equal(dict(kaldi_io.read_mat_ark(str(tmp_path / "cm.ark")))["cm"], g["ref_cm"])         # 'CM ' decode equal
+    assert np.array_equal(dict(kaldi_io.read_mat_ark(str(tmp_path / "txt.ark")))["tx"], g["ref_txt"])
     rd = kaldi_io.PackedArkReader(open(tmp_path / "cm.ark", "rb"))
-    assert rd.peek_dim() == cols
-    buf = np.empty((64, cols), np.float32)
+    assert rd.peek_dim() == g["ref_cm"].shape[1]
+    buf = np.empty((64, g["ref_cm"].shape[1]), np.float32)
     keys, offs, n = rd.read_group(buf)
-    assert keys == ["cm"] and np.array_equal(buf[:n], np.load(tmp_path / "ref_cm.npy"))
+    assert keys == ["cm"] and np.array_equal(buf[:n], g["ref_cm"])
 
 
 def test_matrix_rows_reads_compressed_headers_and_scp_ranges(tmp_path):

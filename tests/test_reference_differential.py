@@ -1,13 +1,11 @@
-"""Build-container only: option combinations that no committed fixture covers, run through the REFERENCE itself (a subprocess
-of oracle/gen_golden.py --adhoc: the reference's blueprint + its own extract_embedding() on CPU) and through this repository's
-recorder + graph passes + numpy interpreter.  The committed goldens pin the BASELINE configurations and every pooling; this
-widens the pinned option space of the blueprints (activation / BN placement / SE / skip / positions / trunk shapes) without
-adding fixtures.  Skipped where /root/reference does not exist (the GPU box)."""
+"""Option combinations that no other committed fixture covers, run through the REFERENCE itself (oracle/gen_golden.py --adhoc:
+the reference's blueprint + its own extract_embedding() on CPU; oracle/gen_reference_checks_golden.py collects those embeddings
+into tests/golden/reference_differential.npz) and through this repository's recorder + graph passes + numpy interpreter.  The
+other goldens pin the BASELINE configurations and every pooling; this widens the pinned option space of the blueprints
+(activation / BN placement / SE / skip / positions / trunk shapes)."""
 
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,8 +13,7 @@ import pytest
 import helpers
 import ir_interp
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "pytorch", "model")), reason="needs the reference tree (build container only)")
+GOLDEN = os.path.join(helpers.REPO, "tests", "golden", "reference_differential.npz")
 
 BN_AFFINE = "'bn_params':{'momentum':0.5,'affine':True,'track_running_stats':True}"
 SMALL_ECAPA = "ecapa_params={'channels':256,'embd_dim':96,'mfa_conv':512}"
@@ -66,17 +63,22 @@ CASES = [
 ]
 
 
+def spec_of(case):
+    """The case as oracle/gen_golden.py --adhoc takes it (and as the fixture records it)."""
+    blueprint, creation, dim, utts, wseed, tol = case
+    return dict(blueprint=blueprint, creation=creation, dim=dim, utts=[list(u) for u in utts], wseed=wseed)
+
+
 @pytest.mark.parametrize("case", CASES, ids=[c[1][:60] for c in CASES])
-def test_option_combinations_against_the_reference_itself(case, tmp_path):
+def test_option_combinations_against_the_reference_itself(case):
     import torch
     from libs.amd import ir, synth
     blueprint, creation, dim, utts, wseed, tol = case
-    out = str(tmp_path / "adhoc.npz")
-    spec = dict(blueprint=blueprint, creation=creation, dim=dim, utts=[list(u) for u in utts], wseed=wseed)
-    r = subprocess.run([sys.executable, os.path.join(helpers.REPO, "oracle", "gen_golden.py"), "--adhoc", json.dumps(spec), out],
-                       capture_output=True, text=True, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = np.load(out)["embeddings"]
+    g = np.load(GOLDEN)
+    specs = json.loads(str(g["meta"]))
+    assert spec_of(case) in specs, "case not in the fixture: rerun oracle/gen_reference_checks_golden.py"
+    ref = g["case%02d" % specs.index(spec_of(case))]
+    assert len(ref) == len(utts)
     model = helpers.build_model(blueprint, creation)
     sd = synth.synth_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}, wseed)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})

@@ -7,7 +7,7 @@ out=gpurun_out/${tag}_lib_ab.txt
 : > $out
 run() {   # label, lib ('' = default), model
   local t0=$(date +%s.%N)
-  local line=$(ASV_AMD_LIB=$2 timeout 120 python bench.py --model $3 --no-supplementary --cpu-seconds 0 --min-seconds 0.6 2>/dev/null | tail -1)
+  local line=$(ASV_AMD_LIB=$2 timeout 120 python bench.py --full --model $3 --no-supplementary --cpu-seconds 0 --min-seconds 0.6 2>/dev/null | tail -1)
   python - "$1" "$3" "$line" >> $out <<'PY'
 import json, sys
 label, model, line = sys.argv[1:4]

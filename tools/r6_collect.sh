@@ -19,7 +19,7 @@ mkdir -p $out
 ( cd $root && timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/${tag}_smoke.txt 2>&1; tail -2 $out/${tag}_smoke.txt; grep sha256 $out/${tag}_smoke.txt > $out/${tag}_library_hash.txt )
 cd /tmp && export TMPDIR=/tmp
 t0=$(date +%s)
-python $root/bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python $root/bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 echo "bench.py wall seconds: $(( $(date +%s) - t0 ))" | tee $out/${tag}_bench_wall.txt
 cp $out/bench_full.json $out/${tag}_bench_full.json 2>/dev/null
 tail -1 $out/${tag}_bench.json | wc -c
@@ -27,13 +27,13 @@ tail -1 $out/${tag}_bench.json | cut -c1-300
 one="--streams 1 --cpu-seconds 0 --no-supplementary --eer-trials 0 --no-traffic --gate-seeds 0"
 for m in "xvector bf16" "xvector f32m" "xvector f32x" "ecapa bf16" "ecapa f32m" "resnet bf16" "resnet f32x"; do
   set -- $m; model=$1; prec=$2; name=$model; [ "$prec" != bf16 ] && name=${model}_$prec
-  python $root/bench.py --model $model --precision $prec $one --per-op > $out/${tag}_${name}.json 2> $out/${tag}_${name}_perop.txt
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_kt_$name -- python $root/bench.py --model $model --precision $prec $one > /dev/null 2>&1
+  python $root/bench.py --full --model $model --precision $prec $one --per-op > $out/${tag}_${name}.json 2> $out/${tag}_${name}_perop.txt
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_kt_$name -- python $root/bench.py --full --model $model --precision $prec $one > /dev/null 2>&1
   cp $out/${tag}_kt_$name/*/*kernel_stats.csv $out/${tag}_${name}_kernel_stats.csv 2>/dev/null
   rm -rf $out/${tag}_kt_$name
 done
 short="--steps 4 --warmup 2 --no-profile --min-seconds 0.05 $one"
-( for prec in bf16 f32m; do echo "== $prec"; ASV_AMD_CHAIN_DBG=1 python $root/bench.py --precision $prec $short 2>&1 >/dev/null | grep "chain dbg" | tail -2 | cut -c1-400; done ) > $out/${tag}_chain_stamps.txt
+( for prec in bf16 f32m; do echo "== $prec"; ASV_AMD_CHAIN_DBG=1 python $root/bench.py --full --precision $prec $short 2>&1 >/dev/null | grep "chain dbg" | tail -2 | cut -c1-400; done ) > $out/${tag}_chain_stamps.txt
 cat $out/${tag}_chain_stamps.txt | cut -c1-200
 ( cd $root && timeout 900 python tools/bench_loaders.py --utts 50000 --ragged-utts 20000 --repeats 2 > $out/${tag}_loaders.json 2> $out/${tag}_loaders.txt; cat $out/${tag}_loaders.txt )
 if [ "$do_pmc" = "pmc" ]; then
@@ -43,12 +43,12 @@ if [ "$do_pmc" = "pmc" ]; then
   for cfg in "xvector bf16" "xvector f32m" "ecapa bf16" "ecapa f32m"; do
     set -- $cfg; model=$1; prec=$2
     for c in FETCH_SIZE WRITE_SIZE; do
-      timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/${tag}_pmc_${model}_${prec}_$c -- python $root/bench.py --model $model --precision $prec $short > /dev/null 2>&1
+      timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/${tag}_pmc_${model}_${prec}_$c -- python $root/bench.py --full --model $model --precision $prec $short > /dev/null 2>&1
       echo "pmc $model $prec $c rc=$?"
       python $root/tools/pmc_per_kernel.py $out/${tag}_pmc_${model}_${prec}_$c/*/*counter_collection.csv $out/${tag}_pmc_${model}_${prec}_${c}_per_kernel.csv 2>/dev/null
       rm -rf $out/${tag}_pmc_${model}_${prec}_$c
     done
-    timeout 300 rocprofv3 --pmc $sq --kernel-trace --output-format csv -d $out/${tag}_pmc_sq_${model}_$prec -- python $root/bench.py --model $model --precision $prec $short > /dev/null 2>&1
+    timeout 300 rocprofv3 --pmc $sq --kernel-trace --output-format csv -d $out/${tag}_pmc_sq_${model}_$prec -- python $root/bench.py --full --model $model --precision $prec $short > /dev/null 2>&1
     clk=""; [ "$model" = xvector ] && [ "$prec" = bf16 ] && [ -n "$clk_bf16" ] && clk="--clock tdnn_chain_kernel=$clk_bf16"
     [ "$model" = xvector ] && [ "$prec" = f32m ] && [ -n "$clk_f32m" ] && clk="--clock tdnn_chainm_kernel=$clk_f32m"
     python $root/tools/sq_summary.py $out/${tag}_pmc_sq_${model}_$prec/*/*counter_collection.csv $out/${tag}_pmc_sq_${model}_$prec/*/*kernel_trace.csv $out/${tag}_sq_${model}_$prec.json $clk > /dev/null 2>&1
