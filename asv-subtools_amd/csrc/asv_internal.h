@@ -212,7 +212,7 @@ struct TdnnChainParams {
   int n128, n_tail, tail_rows;  // 16-bit chain: the launch's tile plan (chain_tile_plan): n128 tiles of 128 frames, then n_tail of tail_rows (96 | 64)
   int row_base, tile_base;      // set by the launcher per kernel launch: first row / first partial-moment block of that launch
   int x_image;                  // f32m chain: the first layer's input rows are images (TdnnKernelParams::x_image): no window conversion
-  int abl;                      // f32m chain, developer aid with ASV_AMD_CHAIN_DBG (ASV_AMD_CHAINM_ABL; results are garbage): bit 0 no in-loop conversion, 1 no in-loop window DMA, 2 no chunk barrier (these three: garbage results), 3 no alternating issue priority (results unchanged)
+  int abl;                      // f32m chain, developer build only (ASV_AMD_CHAINM_ABL; 0 in libasv_amd.so): bit 0 no in-loop conversion, 1 no in-loop window DMA, 2 no chunk barrier (these three: garbage results), 3 no alternating issue priority (results unchanged)
 };
 // How the 16-bit chain kernel cuts `rows` (a multiple of 128) into tiles.  One workgroup per CU (160 KiB of LDS), so:
 //   * a batch that does not fill ONE round of the chip's CUs in 128-frame tiles runs in the smallest tile - 64 or 96 frames -
@@ -242,9 +242,6 @@ int launch_tdnn_chain4(const TdnnChainParams &p, hipStream_t s);
 int launch_tdnn_chainx(const TdnnChainParams &p, hipStream_t s);
 // the same with the two correction products on the block-scaled 8-bit matrix instruction ("f32m", ASV_FLAG_X3_MX8; kernels_tdnn_chainm.hip)
 int launch_tdnn_chainm(const TdnnChainParams &p, hipStream_t s);
-// ... in 96-frame tiles (kernels_tdnn_chainm96.hip): 1.5 x the matrix work per byte of the weight stream that bounds the 64-frame kernel
-int chainm96_tiles(int rows);
-int launch_tdnn_chainm96(const TdnnChainParams &p, hipStream_t s);
 // ECAPA Res2NetBlock as one kernel (kernels_res2.hip)
 constexpr int kRes2Width = 128;
 struct Res2KernelParams {

@@ -103,7 +103,7 @@ void pack_tdnn_weight_x3p(const float *w, int out_ch, int in_ch, int tot_ctx, in
 // [32-channel output fragment][tap][32-channel input group][lane = (lh, output channel lr)][16]: plane 0 = e4m3(lo 2^6) (|lo| <= 2^-11 |hi|,
 // hi < 2^14 under x3_weight_scale), plane 1 = e4m3(hi 2^-6).  Byte q of lane half lh = input channel 32 group + (q < 8 ? 8 lh + q :
 // 16 + 8 lh + q - 8) - the channels the lane's two half fragments of the group hold, in their order, so that a kernel may also MAKE plane 1
-// from those half fragments in registers (v_cvt_scalef32_pk_fp8_f16: kernels_tdnn_x3m.hip and the 96-frame chain do; the 64-frame chain
+// from those half fragments in registers (v_cvt_scalef32_pk_fp8_f16: kernels_tdnn_x3m.hip does; the chain kernel kernels_tdnn_chainm.hip
 // fetches it - 24 conversions per K step cost its waves more issue time than two more 16-byte loads, profiles/r6s_*).  The kernels' block
 // scales undo the 2^6 / 2^-6.
 size_t tdnn_weight_mx8_plane_bytes(int cout_pad, int cin_pad, int n_taps) { return (size_t)(cout_pad / 32) * n_taps * ((cin_pad + 31) / 32) * 1024; }
@@ -223,7 +223,6 @@ struct asv_net {
   std::vector<DevMem> arena;             // one region per buffer
   DevMem meta_dev;                       // int32 metadata (segments etc.)
   DevMem rowmeta_dev;                    // row_seg / row_valid for both domains
-  DevMem splitk_dev;                     // split-K partial accumulators
   DevMem poolpart_dev;                   // fused-pooling partial moments
   DevMem lde_dev;                        // LDE pooling: per-row centre weights [rows][64]
   void *zero_page = nullptr;             // 256 zero bytes (masked direct-to-LDS loads); bytes 128..131: the status word (asv_net_status)
@@ -466,7 +465,6 @@ void asv_net_destroy(asv_net_t *net) {
   for (auto &m : net->arena) if (m.ptr) (void)hipFree(m.ptr);
   if (net->meta_dev.ptr) (void)hipFree(net->meta_dev.ptr);
   if (net->rowmeta_dev.ptr) (void)hipFree(net->rowmeta_dev.ptr);
-  if (net->splitk_dev.ptr) (void)hipFree(net->splitk_dev.ptr);
   if (net->poolpart_dev.ptr) (void)hipFree(net->poolpart_dev.ptr);
   if (net->lde_dev.ptr) (void)hipFree(net->lde_dev.ptr);
   if (net->zero_page) (void)hipFree(net->zero_page);
@@ -1164,6 +1162,30 @@ struct DomainRun {
   uint32_t *row_valid = nullptr;
 };
 
+// Kernel-selection switches of the TDNN layers (developer A/B aids, result-preserving), read once per process unless ASV_AMD_LIVE_TUNE is set -
+// the in-process A/B tests switch that on after the library's first launch, so THAT lookup cannot be cached: one getenv per run
+struct TdnnRules {
+  int p8 = 1, p8x = 1, x3m = 1, x3m_image = 1;   // ASV_AMD_P8 / _P8X / _X3M / _X3M_IMAGE: 0 off, 1 the production rule, N > 1 a lowered tile count
+  long long cus = 256;                           // "one round of tiles" = one 256 x 256 tile per CU of THIS device (the kernels size their persistent grids from the same count)
+  int chain_dbg = 0;                             // ASV_AMD_CHAIN_DBG (read once): the chain kernels' phase stamps on stderr, levels 1 - 4
+};
+TdnnRules tdnn_rules() {
+  auto env = [](const char *name) { const char *v = getenv(name); return v != nullptr ? atoi(v) : 1; };
+  static const TdnnRules once = [&] {
+    TdnnRules r;
+    r.p8 = env("ASV_AMD_P8"); r.p8x = env("ASV_AMD_P8X"); r.x3m = env("ASV_AMD_X3M"); r.x3m_image = env("ASV_AMD_X3M_IMAGE");
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    r.cus = n > 0 ? n : 256;
+    const char *dbg = getenv("ASV_AMD_CHAIN_DBG");
+    r.chain_dbg = dbg != nullptr ? std::max(1, atoi(dbg)) : 0;
+    return r;
+  }();
+  TdnnRules r = once;
+  if (getenv("ASV_AMD_LIVE_TUNE") != nullptr) { r.p8 = env("ASV_AMD_P8"); r.p8x = env("ASV_AMD_P8X"); r.x3m = env("ASV_AMD_X3M"); r.x3m_image = env("ASV_AMD_X3M_IMAGE"); }
+  return r;
+}
+
 struct RunCtx {
   asv_net *net; hipStream_t s; BatchPlan bp;
   float *final_out = nullptr;      // asv_net_extract: the caller's result matrix (lets the last layer write it directly)
@@ -1171,6 +1193,7 @@ struct RunCtx {
   int32_t *seg_src0, *seg_frames, *utt_seg0, *utt_nseg;     // device metadata
   std::vector<DomainRun> dom;
   std::vector<char> buf_image;     // per run: buffer holds images (TdnnKernelParams::y_image of its producer)
+  TdnnRules rules;                 // per run (run_ops)
 };
 
 // what prepare() leaves behind for the next call with identical offsets
@@ -1264,30 +1287,216 @@ unsigned char *view(RunCtx &c, int buf, int ch_off) {
   return reinterpret_cast<unsigned char *>(c.net->arena[buf].ptr) + (size_t)ch_off * c.net->elem_size(b.domain);
 }
 
+// ---- TDNN layers: which kernel runs an op (choose_tdnn), and the pieces of its launch
+
+// The kernel of a TDNN op: the head of a layer chain (the op, its 1-tap followers and the fused statistics pooling in one kernel),
+// or one per-layer kernel.
+enum class TdnnPath {
+  Chain16, ChainX, ChainM,                        // kernels_tdnn_chain.hip (16-bit modes) / kernels_tdnn_chainx.hip (f32x) / kernels_tdnn_chainm.hip (f32m)
+  Ref, Utts,                                      // plain-VALU self-check kernels / the pooled-domain GEMM (kernels_utts.hip)
+  ConvNarrow, ConvWide, ConvS2d, ConvC1, ConvX3,  // grid convolutions of the 2-D trunk (kernels_conv2d.hip, kernels_conv2d_x3.hip)
+  X3m, P8x, X3, P8, Big3, Mfma                    // frame layers
+};
+struct TdnnChoice {
+  TdnnPath path = TdnnPath::Mfma;
+  ChainTilePlan plan;          // Chain16: the launch's tile plan
+  int n_blocks = 0;            // chains: partial-moment blocks
+  int pool_slots = 0;          // > 0: the fused statistics pooling is taken (chains: always), at most this many segments per block
+  int min_len = 0;             // chains: the batch's shortest segment in frames
+  bool chain() const { return path == TdnnPath::Chain16 || path == TdnnPath::ChainX || path == TdnnPath::ChainM; }
+};
+
+// the most segments of the frames domain that any one block of rows holds (block_of: row -> block, at most n_blocks)
+template <class BlockOf> int max_segments_per_block(const DomainPlan &fp, int n_blocks, BlockOf block_of) {
+  std::vector<int> per_block((size_t)n_blocks + 1, 0);
+  int slots = 1;
+  for (size_t s = 0; s < fp.seg_row0.size(); ++s)
+    for (int h = block_of(fp.seg_row0[s]); h <= block_of(fp.seg_row0[s] + fp.seg_len[s] - 1); ++h) slots = std::max(slots, ++per_block[h]);
+  return slots;
+}
+
+// The kernel of TDNN op k (p: its kernel parameters, fill_tdnn_params in run_ops).  run_ops launches by it, and asks it in advance about the
+// op that will read a layer's output (reader_takes_image), so the two always agree.
+TdnnChoice choose_tdnn(const RunCtx &c, size_t k, const TdnnKernelParams &p) {
+  const asv_net *net = c.net;
+  const Op &op = net->ops[k];
+  const TdnnRules &r = c.rules;
+  const DomainPlan &fp = c.bp.dom[ASV_DOMAIN_FRAMES];
+  const bool use_ref = (net->flags & ASV_FLAG_REF_KERNELS) != 0, small = (net->flags & ASV_FLAG_SMALL_TILES) != 0;
+  const bool h16 = p.et != ET_F32;              // 16-bit rows (bf16 or half)
+  TdnnChoice ch;
+  // tdnn -> [1-tap]* -> 1-tap + pooling in one kernel, if the batch allows the fused pooling: at most 16 segments per block (a crowd of
+  // tiny utterances takes the per-layer kernels and the separate pooling kernel)
+  if (op.chain_last >= 0 && !use_ref && (h16 || net->x3()) && p.halo <= kHalo && !small &&
+      (net->x3() || (unsigned long long)p.rows * (unsigned long long)p.ldx * 2ull < (1ull << 32))) {
+    if (net->x3()) {
+      // f32x: the split-product chain on 64-row tiles; f32m: the chain with its correction products on the scaled 8-bit instruction, when
+      // every layer of it has 8-bit fragments - in 64-frame tiles too
+      bool mx = net->x3_mx();
+      for (size_t j = k; j <= (size_t)op.chain_last && mx; ++j) mx = (net->ops[j].wfrag_fold != nullptr ? net->ops[j].w8_fold : net->ops[j].w8) != nullptr;
+      ch.path = mx ? TdnnPath::ChainM : TdnnPath::ChainX;
+      ch.n_blocks = p.rows >> 6;
+      ch.pool_slots = max_segments_per_block(fp, ch.n_blocks, [](int row) { return row >> 6; });
+    } else {
+      // the 16-bit chain runs batches of less than one round of workgroups in 96- / 64-frame tiles (ChainTilePlan); developer runs with
+      // phase stamps keep 128-frame tiles throughout
+      ch.path = TdnnPath::Chain16;
+      ch.plan = chain_tile_plan(p.rows, r.chain_dbg == 0);
+      ch.n_blocks = ch.plan.tiles();
+      ch.pool_slots = max_segments_per_block(fp, ch.n_blocks, [&](int row) { return ch.plan.tile_of(row); });
+    }
+    if (ch.pool_slots <= 16) {
+      ch.min_len = 1 << 30;
+      for (int32_t len : fp.seg_len) ch.min_len = std::min(ch.min_len, (int)len);
+      return ch;
+    }
+    ch = TdnnChoice();
+  }
+  // fused statistics pooling: needs few enough segments per 128-row half-tile (i.e. no tiny utterances)
+  int slots = 0;
+  if (op.fused_pool >= 0 && !use_ref && !small) {
+    slots = max_segments_per_block(fp, fp.rows_pad / 128, [](int row) { return row >> 7; });
+    if (slots > 16) slots = 0;                  // many tiny utterances: use the separate pooling kernel
+  }
+  const bool big3 = !use_ref && p.halo <= kHalo && !small && tdnn_big3_supported(p, p.et, !h16);
+  const bool x3 = !use_ref && !op.utts && net->x3() && !small && tdnn_x3_supported(p);
+  const bool fuse = slots > 0 && (big3 || (x3 && tdnn_x3_pool_supported(p)));
+  if (fuse) ch.pool_slots = slots;
+  const long long tiles256 = (long long)(p.rows / 256) * (round_up(p.cout_store, 256) / 256);
+  // Round 5: the layers of the variant-3 kernel with the plain epilogue, whole 64-channel chunks and at least one round of 256 x 256
+  // tiles on the chip's CUs go to the 8-phase kernel (kernels_tdnn_p8.hip: both operands through LDS-DMA, staggered wave rows;
+  // bit-identical outputs, 1.03 - 1.15 x the rate: profiles/r5e_p8_shapes.txt).  ASV_AMD_P8=0: the variant-3 kernel everywhere.
+  const bool p8 = big3 && !fuse && r.p8 != 0 && tdnn_p8_supported(p, p.et, !h16) && tiles256 >= (r.p8 > 1 ? r.p8 : r.cus);
+  // f32x: the 8-phase three-product kernel takes the wide plain layers that fill whole rounds of 256 x 256 tiles (kernels_tdnn_p8x.hip; the
+  // bits of tdnn_gemm_x3_kernel; ASV_AMD_P8X=0: off).  Production rule: at least one round of tiles AND a last round that is >= 85 % full -
+  // the x-vector's tdnn2 at 256 utterances is 408 tiles = 1.6 rounds, where the finer 128-row tiles of tdnn_gemm_x3_kernel are as fast and
+  // leave CUs to the other stream: -0.9 % on two streams, profiles/r5s_p8x_model_ab.txt; ECAPA's layers are 4.75 and 7.1 rounds
+  const bool p8x = x3 && !fuse && r.p8x != 0 && tdnn_p8x_supported(p) &&
+                   (r.p8x > 1 ? tiles256 >= r.p8x : (tiles256 >= r.cus && tiles256 * 100 >= ((tiles256 + r.cus - 1) / r.cus) * r.cus * 85));
+  // f32m: the 128-row kernel with its correction products on the scaled 8-bit instruction, where the three-product kernel would take its
+  // 128-row tiles (ASV_AMD_X3M=0: off) and the 8-phase kernel does not (its fill rule: the x-vector's tdnn1 / tdnn2 - 163 us here against
+  // 227 on the three-product kernel, profiles/r6f_*).  ECAPA's wide 1-tap layers stay on the 8-phase kernel: a new window (barrier +
+  // conversion) per 32 channels makes this kernel only 4 - 12 % faster there on one stream and 8 % slower in the two-stream pipeline
+  // (35.1 k against 38.2 k utterances/s, profiles/r6q_bench_line.json)
+  const bool x3m = x3 && !fuse && !p8x && r.x3m != 0 && net->x3_mx() && tdnn_x3m_supported(p) &&
+                   (long long)(p.rows / 128) * (round_up(p.cout_store, 256) / 256) >= (r.x3m > 1 ? r.x3m : 384);      // (384: where the three-product kernel takes its 128-row tiles)
+  const bool grid = !use_ref && net->domains[net->bufs[op.tdnn.in_buf].domain].kind == 2 && !small;
+  if (use_ref) ch.path = TdnnPath::Ref;
+  else if (op.utts) ch.path = TdnnPath::Utts;
+  else if (grid && grid_conv_narrow_supported(p, p.et)) ch.path = TdnnPath::ConvNarrow;
+  else if (grid && grid_conv_wide_supported(p, p.et)) ch.path = TdnnPath::ConvWide;
+  else if (grid && grid_conv_s2d_supported(p, p.et)) ch.path = TdnnPath::ConvS2d;
+  else if (grid && grid_conv_c1_supported(p, p.et, op.tdnn.in_ch)) ch.path = TdnnPath::ConvC1;
+  else if (x3m) ch.path = TdnnPath::X3m;
+  else if (p8x) ch.path = TdnnPath::P8x;
+  else if (x3) ch.path = TdnnPath::X3;
+  else if (net->x3() && !small && grid_conv_x3_supported(p)) ch.path = TdnnPath::ConvX3;
+  else if (p8) ch.path = TdnnPath::P8;
+  else if (big3) ch.path = TdnnPath::Big3;
+  return ch;
+}
+
+// Developer aid (ASV_AMD_CHAIN_DBG = 1 - 4): the chain kernel's phase stamps ([workgroup][wave][32] s_memtime values) summarised on stderr;
+// frees the stamp buffer
+int report_chain_stamps(void *dbg, size_t nwg, int chain_dbg, bool chain_mx, hipStream_t s) {
+  std::vector<unsigned long long> h(nwg * 8 * 32);
+  ASV_HIP_CHECK(hipStreamSynchronize(s));
+  ASV_HIP_CHECK(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
+  ASV_HIP_CHECK(hipFree(dbg));
+  double sum[32] = {0}; size_t cnt = 0; double cyc = 0, rt = 0;
+  for (size_t w = 0; w < nwg * 8; ++w) {
+    const unsigned long long *t = &h[w * 32];
+    if (t[0] == 0) continue;
+    for (int k = 1; k < 14; ++k) if (t[k] > t[k - 1]) sum[k] += (double)(t[k] - t[k - 1]);      // 13: the 4-wave kernel's drain
+    if (chain_dbg >= 3) {
+      if (t[16] > t[7]) sum[16] += (double)(t[16] - t[7]);                                   // unit's K loop end -> epilogue body
+      for (int k = 17; k < 22; ++k) if (t[k] > t[k - 1]) sum[k] += (double)(t[k] - t[k - 1]);
+    }
+    const unsigned long long t_end = t[13] > t[12] ? t[13] : t[12];
+    if (t_end > t[0] && t[15] > t[14]) { cyc += (double)(t_end - t[0]); rt += (double)(t[15] - t[14]); }
+    ++cnt;
+  }
+  fprintf(stderr, "[chain dbg] %zu waves, mean cycles per phase:", cnt);
+  fprintf(stderr, " [shader clock %.0f MHz, %.1f us per workgroup]", rt > 0 ? 100.0 * cyc / rt : 0.0, cnt ? rt / 100.0 / (double)cnt : 0.0);
+  for (int k = 1; k < 14; ++k) if (k < 13 || sum[k] > 0) fprintf(stderr, " %d:%.0f", k, sum[k] / (double)std::max<size_t>(cnt, 1));
+  if (chain_dbg >= 3) {
+    fprintf(stderr, " | first epilogue: entry %.0f, fragments", sum[16] / (double)std::max<size_t>(cnt, 1));
+    for (int k = 17; k < 21; ++k) fprintf(stderr, " %.0f", sum[k] / (double)std::max<size_t>(cnt, 1));
+    fprintf(stderr, ", publish %.0f", sum[21] / (double)std::max<size_t>(cnt, 1));
+  }
+  fprintf(stderr, "\n");
+  if (chain_mx && chain_dbg >= 3) {                      // layer A, steps 0 .. 14: mean cycles per step, by wave
+    for (int wv = 0; wv < 8; ++wv) {
+      double d[15] = {0}; size_t cn = 0;
+      for (size_t wg = 0; wg < nwg; ++wg) {
+        const unsigned long long *t = &h[(wg * 8 + wv) * 32];
+        if (t[16] == 0 || t[31] <= t[16]) continue;
+        for (int k = 0; k < 15; ++k) d[k] += (double)(t[17 + k] - t[16 + k]);
+        ++cn;
+      }
+      fprintf(stderr, "[chainm dbg] wave %d, cycles of layer A's steps 0..14:", wv);
+      for (int k = 0; k < 15; ++k) fprintf(stderr, " %.0f", d[k] / (double)std::max<size_t>(cn, 1));
+      fprintf(stderr, "\n");
+    }
+  }
+  {                                                       // 4-wave kernel, ablation 8: fine stamps of wave 0's third unit (slots of wave 4..7)
+    double fs[25] = {0}; size_t fc = 0;
+    for (size_t wg = 0; wg < nwg; ++wg) {
+      const unsigned long long *t = &h[(wg * 8 + 4) * 32];
+      if (t[0] == 0 || t[24] <= t[0]) continue;
+      for (int k = 1; k < 25; ++k) fs[k] += (double)(t[k] - t[k - 1]);
+      ++fc;
+    }
+    if (fc) {
+      fprintf(stderr, "[chain dbg] third unit of wave 0, %zu workgroups, per chunk: pre | 32 matrix instructions | post:", fc);
+      for (int c = 0; c < 8; ++c) fprintf(stderr, "  %.0f | %.0f | %.0f", fs[3 * c + 1] / fc, fs[3 * c + 2] / fc, fs[3 * c + 3] / fc);
+      fprintf(stderr, "\n");
+    }
+  }
+  if (chain_dbg == 2 || chain_dbg >= 4) {                 // raw timelines of two workgroups: waves w and w + 4 share a SIMD
+    const size_t picks[2] = {nwg / 4, nwg / 2 + 1};
+    for (size_t wg : picks) {
+      if (wg >= nwg) continue;
+      unsigned long long t0 = ~0ull;
+      for (int w = 0; w < 8; ++w) if (h[(wg * 8 + w) * 32] != 0) t0 = std::min(t0, h[(wg * 8 + w) * 32]);
+      for (int w = 0; w < 8; ++w) {
+        fprintf(stderr, "[chain dbg] workgroup %zu wave %d stamps (cycles since the first wave's stamp 0):", wg, w);
+        for (int k = 0; k < 13; ++k) fprintf(stderr, " %lld", (long long)(h[(wg * 8 + w) * 32 + k] - t0));
+        if (chain_dbg >= 4) { fprintf(stderr, " |"); for (int k = 16; k < 22; ++k) fprintf(stderr, " %lld", (long long)(h[(wg * 8 + w) * 32 + k] - t0)); }
+        fprintf(stderr, "\n");
+      }
+    }
+  }
+  return ASV_OK;
+}
+
+// The second half of a fused statistics pooling (pool op `pool_op`): adds each segment's partial moments in row order, adds the BN
+// shift back to the mean and writes mean || std.  Chain kernels: partials [block][slot][lh][3][ld] (lh_split 1) in 2^tile_shift-row blocks,
+// then the tail blocks of `plan`; per-layer kernels: [128-row tile][slot][3][ld] (lh_split 0, tile_shift 7, an empty plan).
+int finish_fused_pool(RunCtx &c, Prof &prof, int pool_op, const DomainRun &dr, const float *partial, int ld_partial, int slots, int lh_split,
+                      int tile_shift, const ChainTilePlan &plan, const float *shift) {
+  asv_net *net = c.net;
+  const auto &q = net->ops[pool_op].pool;
+  PoolFinishParams f;
+  f.partial = partial; f.ld_partial = ld_partial; f.pool_slots = slots; f.lh_split = lh_split; f.tile_shift = tile_shift;
+  f.rows_shift = plan.rows128(); f.tail_rows = plan.n_tail > 0 ? plan.tail_rows : 0; f.n_shift = plan.n128;
+  f.row_seg = dr.row_seg; f.rows = dr.rows_pad; f.seg_row0 = dr.seg_row0; f.seg_len = dr.seg_len;
+  f.shift = shift;
+  f.out = reinterpret_cast<float *>(net->arena[q.out_buf].ptr) + q.out_ch_off; f.ld_out = net->bufs[q.out_buf].ld; f.channels = q.channels;
+  f.stddev = q.stddev; f.unbiased = q.unbiased; f.var_mode = q.var_mode; f.eps = q.eps;
+  int rc;
+  if ((rc = prof.begin(K_POOL, 0, pool_op))) return rc;
+  if ((rc = launch_pool_finish(f, c.bp.segments, c.s))) return rc;
+  return prof.end();
+}
+
 int run_ops(RunCtx &c, size_t n_ops) {
   asv_net *net = c.net;
   const BatchPlan &bp = c.bp;
   Prof prof{net, c.s};
   int rc;
-  const bool use_ref = (net->flags & ASV_FLAG_REF_KERNELS) != 0;
   c.buf_image.assign(net->bufs.size(), 0);
-  // Kernel-selection switches (developer A/B aids; read once unless ASV_AMD_LIVE_TUNE is set - the in-process A/B tests switch that on
-  // after the library's first launch, so THAT lookup cannot be cached: one getenv per run)
-  const bool live_tune = getenv("ASV_AMD_LIVE_TUNE") != nullptr;
-  auto tune = [&](const char *name, int dflt, int cached) { return live_tune ? (getenv(name) ? atoi(getenv(name)) : dflt) : cached; };
-  static const int p8_env = getenv("ASV_AMD_P8") ? atoi(getenv("ASV_AMD_P8")) : 1;
-  static const int p8x_env = getenv("ASV_AMD_P8X") ? atoi(getenv("ASV_AMD_P8X")) : 1;
-  static const int x3m_env = getenv("ASV_AMD_X3M") ? atoi(getenv("ASV_AMD_X3M")) : 1;
-  static const int img_env = getenv("ASV_AMD_X3M_IMAGE") ? atoi(getenv("ASV_AMD_X3M_IMAGE")) : 1;
-  static const int chainm_rows_env = getenv("ASV_AMD_CHAINM_ROWS") != nullptr ? atoi(getenv("ASV_AMD_CHAINM_ROWS")) : 64;
-  const int p8_on = tune("ASV_AMD_P8", 1, p8_env), p8x_on = tune("ASV_AMD_P8X", 1, p8x_env), x3m_on = tune("ASV_AMD_X3M", 1, x3m_env);
-  const int img_on = tune("ASV_AMD_X3M_IMAGE", 1, img_env), chainm_rows = tune("ASV_AMD_CHAINM_ROWS", 64, chainm_rows_env);
-  // "one round of tiles" = one 256 x 256 tile per CU of THIS device (the kernels size their persistent grids from the same count)
-  static const long long cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return (long long)(n > 0 ? n : 256);
-  }();
+  c.rules = tdnn_rules();
   // the kernel parameters of TDNN op k (views, weights, taps)
   auto fill_tdnn_params = [&](size_t k, TdnnKernelParams &p) {
     const Op &op = net->ops[k];
@@ -1314,60 +1523,13 @@ int run_ops(RunCtx &c, size_t n_ops) {
     p.zero16 = net->zero_page;
     p.wfrag = op.wfrag; p.wlo = op.wlo; p.wconv = op.wconv; p.wx3p = op.wx3p; p.w8 = op.w8;
   };
-  // f32x: the 8-phase three-product kernel takes the wide plain layers that fill whole rounds of 256 x 256 tiles (kernels_tdnn_p8x.hip; the
-  // bits of tdnn_gemm_x3_kernel; ASV_AMD_P8X=0: off).  Production rule: at least one round of tiles AND a last round that is >= 85 % full -
-  // the x-vector's tdnn2 at 256 utterances is 408 tiles = 1.6 rounds, where the finer 128-row tiles of tdnn_gemm_x3_kernel are as fast and
-  // leave CUs to the other stream: -0.9 % on two streams, profiles/r5s_p8x_model_ab.txt; ECAPA's layers are 4.75 and 7.1 rounds
-  auto p8x_rule = [&](const TdnnKernelParams &q, bool x3q, bool fuseq) {
-    const long long tiles = (long long)(q.rows / 256) * (round_up(q.cout_store, 256) / 256);
-    const bool fill = p8x_on > 1 ? tiles >= p8x_on : (tiles >= cus && tiles * 100 >= ((tiles + cus - 1) / cus) * cus * 85);
-    return x3q && !fuseq && p8x_on != 0 && tdnn_p8x_supported(q) && fill;
-  };
-  // f32m: the 128-row kernel with its correction products on the scaled 8-bit instruction, where the three-product kernel would take its
-  // 128-row tiles (ASV_AMD_X3M=0: off) and the 8-phase kernel does not (its fill rule: the x-vector's tdnn1 / tdnn2 - 163 us here against
-  // 227 on the three-product kernel, profiles/r6f_*).  ECAPA's wide 1-tap layers stay on the 8-phase kernel: a new window (barrier +
-  // conversion) per 32 channels makes this kernel only 4 - 12 % faster there on one stream and 8 % slower in the two-stream pipeline
-  // (35.1 k against 38.2 k utterances/s, profiles/r6q_bench_line.json)
-  auto x3m_rule = [&](const TdnnKernelParams &q, bool x3q, bool fuseq) {
-    return x3q && !fuseq && !p8x_rule(q, x3q, fuseq) && x3m_on != 0 && net->x3_mx() && tdnn_x3m_supported(q) &&
-           (long long)(q.rows / 128) * (round_up(q.cout_store, 256) / 256) >= (x3m_on > 1 ? x3m_on : 384);      // (384: where the three-product kernel takes its 128-row tiles)
-  };
-  auto x3_rule = [&](const Op &o, const TdnnKernelParams &q) {
-    return !use_ref && !o.utts && net->x3() && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && tdnn_x3_supported(q);
-  };
-  // the chain kernels' fused pooling: utterances per block of `block_rows` rows, worst block (a crowd of tiny utterances -> per-layer path)
-  auto chain_slots_uniform = [&](int block_rows, int n_blocks, int *min_len) {
-    const DomainPlan &fp = bp.dom[ASV_DOMAIN_FRAMES];
-    std::vector<int> per_block((size_t)n_blocks + 1, 0);
-    int slots = 1, ml = 1 << 30;
-    for (size_t sidx = 0; sidx < fp.seg_len.size(); ++sidx) ml = std::min(ml, (int)fp.seg_len[sidx]);
-    for (size_t sidx = 0; sidx < fp.seg_row0.size(); ++sidx)
-      for (int h = fp.seg_row0[sidx] / block_rows; h <= (fp.seg_row0[sidx] + fp.seg_len[sidx] - 1) / block_rows; ++h) slots = std::max(slots, ++per_block[h]);
-    if (min_len != nullptr) *min_len = ml;
-    return slots;
-  };
-  auto chain_is_mx = [&](size_t head) {
-    bool mx = net->x3() && net->x3_mx();
-    for (size_t k = head; k <= (size_t)net->ops[head].chain_last && mx; ++k)
-      mx = (net->ops[k].wfrag_fold != nullptr ? net->ops[k].w8_fold : net->ops[k].w8) != nullptr;
-    return mx;
-  };
-  auto chain_branch = [&](const Op &o, const TdnnKernelParams &q, bool rows16) {      // the condition under which op o runs as the head of a chain kernel
-    return o.chain_last >= 0 && !use_ref && (rows16 || net->x3()) && q.halo <= kHalo && (net->flags & ASV_FLAG_SMALL_TILES) == 0 &&
-           (net->x3() || (unsigned long long)q.rows * (unsigned long long)q.ldx * 2ull < (1ull << 32));
-  };
-  // f32m, op j reads ONE buffer as its input rows (Op::image_reader of the producer): will it, in THIS run, go to a kernel that reads
-  // images?  Follows the selection below step by step - the chain branch first, then the per-layer rules - and the launches check it.
+  // f32m, op j reads ONE buffer as its input rows (Op::image_reader of the producer): will it, in THIS run, go to a kernel that reads images?
   auto reader_takes_image = [&](size_t j) {
-    const Op &o = net->ops[j];
     TdnnKernelParams q;
     fill_tdnn_params(j, q);
-    if (chain_branch(o, q, false)) {
-      const bool mx = chain_is_mx(j), mx96 = mx && chainm_rows == 96 && q.rows >= 96;
-      const int slots = mx96 ? chain_slots_uniform(96, chainm96_tiles(q.rows), nullptr) : chain_slots_uniform(64, q.rows >> 6, nullptr);
-      if (slots <= 16) return mx && !mx96 && q.cin_pad % 32 == 0;
-    }
-    return o.fused_pool < 0 && x3m_rule(q, x3_rule(o, q), false) && tdnn_x3m_image_in_supported(q);
+    const TdnnChoice r = choose_tdnn(c, j, q);
+    return (r.path == TdnnPath::ChainM && q.cin_pad % 32 == 0) ||
+           (r.path == TdnnPath::X3m && net->ops[j].fused_pool < 0 && tdnn_x3m_image_in_supported(q));
   };
   for (size_t i = 0; i < n_ops; ++i) {
     Op &op = net->ops[i];
@@ -1377,208 +1539,74 @@ int run_ops(RunCtx &c, size_t n_ops) {
         const int domid = net->bufs[d.in_buf].domain;
         const DomainRun &dr = c.dom[domid];
         const int et = net->dom_et(domid);
-        const bool bf16 = et != ET_F32;              // 16-bit rows (bf16 or half)
+        const bool h16 = et != ET_F32;               // 16-bit rows (bf16 or half)
         TdnnKernelParams p;
         fill_tdnn_params(i, p);
         p.x_image = c.buf_image[d.in_buf];
-        const bool chain_x3 = net->x3();             // f32x: the split-product chain on 64-row tiles (kernels_tdnn_chainx.hip)
-        if (chain_branch(op, p, bf16)) {
-          // tdnn -> [1-tap]* -> 1-tap + pooling in one kernel, if the batch allows the fused pooling (no crowd of tiny utterances)
-          const DomainPlan &fp = bp.dom[ASV_DOMAIN_FRAMES];
-          const int tshift = chain_x3 ? 6 : 7;         // rows per pooling partial: the kernel's tile
-          // the 16-bit chain runs batches of less than one round of workgroups in 96- / 64-frame tiles (ChainTilePlan); developer
-          // runs with phase stamps keep 128-frame tiles throughout
-          static const bool chain_dbg_on = getenv("ASV_AMD_CHAIN_DBG") != nullptr;
-          ChainTilePlan plan;
-          if (!chain_x3) plan = chain_tile_plan(p.rows, !chain_dbg_on);
-          // f32m: the chain with its correction products on the scaled 8-bit instruction, when every layer of it has 8-bit fragments - in
-          // 64-frame tiles (kernels_tdnn_chainm.hip).  ASV_AMD_CHAINM_ROWS=96 selects the 96-frame kernel (kernels_tdnn_chainm96.hip: the same
-          // results, measured 13 % SLOWER - 507.6 against 450.1 us on one box, profiles/r6r_*: kept as the measurement it is)
-          const bool chain_mx = chain_x3 && chain_is_mx(i);
-          const bool mx96 = chain_mx && chainm_rows == 96 && p.rows >= 96;
-          const int n_blocks = mx96 ? chainm96_tiles(p.rows) : (chain_x3 ? (p.rows >> tshift) : plan.tiles());
-          int slots = 1, min_len = 1 << 30;
-          if (chain_x3) {
-            slots = chain_slots_uniform(mx96 ? 96 : 64, n_blocks, &min_len);
-          } else {
-            std::vector<int> per_half((size_t)n_blocks + 1, 0);
-            for (size_t sidx = 0; sidx < fp.seg_len.size(); ++sidx) min_len = std::min(min_len, (int)fp.seg_len[sidx]);
-            for (size_t sidx = 0; sidx < fp.seg_row0.size(); ++sidx)
-              for (int h = plan.tile_of(fp.seg_row0[sidx]); h <= plan.tile_of(fp.seg_row0[sidx] + fp.seg_len[sidx] - 1); ++h) slots = std::max(slots, ++per_half[h]);
+        const TdnnChoice ch = choose_tdnn(c, i, p);
+        if (ch.chain()) {
+          ASV_REQUIRE(!p.x_image || ch.path == TdnnPath::ChainM, "tdnn(chain): image rows reached a chain kernel that cannot read them (internal)");
+          const size_t l = (size_t)op.chain_last;
+          Op &lo = net->ops[l];
+          TdnnChainParams cp;
+          memset(&cp, 0, sizeof(cp));
+          cp.x = p.x; cp.ldx = p.ldx; cp.rows = p.rows; cp.cin_pad = p.cin_pad; cp.n_taps = p.n_taps;
+          for (int t = 0; t < p.n_taps; ++t) cp.taps[t] = p.taps[t];
+          // a layer whose consumer holds folded weights (wfrag_fold) stores ReLU(acc) only: its scale / shift are not passed
+          auto layer_of = [&](size_t k) {
+            const Op &o = net->ops[k];
+            const bool folded_in = o.wfrag_fold != nullptr;                                  // the previous layer's BN sits in these weights
+            const bool folded_out = k < l && net->ops[k + 1].wfrag_fold != nullptr;          // this layer's BN sits in the next layer's
+            TdnnChainLayer L;
+            L.wfrag = folded_in ? o.wfrag_fold : o.wfrag; L.bias = folded_in ? o.bias_fold : o.bias;
+            L.wlo = folded_in ? o.wlo_fold : o.wlo; L.w_scale = folded_in ? o.w_scale_fold : o.w_scale;
+            L.w8 = folded_in ? o.w8_fold : o.w8;
+            L.scale = folded_out ? nullptr : o.scale; L.shift = folded_out ? nullptr : o.shift;
+            L.relu = o.tdnn.act1 == ASV_ACT_RELU; L.cout_pad = o.cout_pad;
+            return L;
+          };
+          cp.first = layer_of(i);
+          cp.n_mid = (int)(l - i - 1);
+          for (size_t k = i + 1; k < l; ++k) cp.mid[k - i - 1] = layer_of(k);
+          cp.last = layer_of(l);
+          cp.pool_slots = ch.pool_slots; cp.ld_partial = lo.cout_pad; cp.row_seg = dr.row_seg;
+          cp.et = ch.path == TdnnPath::Chain16 ? et : net->x3_et();
+          cp.min_seg_len = ch.min_len;
+          cp.status = status_word(net);
+          cp.x_image = p.x_image ? 1 : 0;
+#ifdef ASV_WITH_ABLATION
+          // developer build only: ASV_AMD_CHAINM_GROUP=0 reads image rows under the per-chunk protocol of the f32 rows (a measuring aid,
+          // same results); ASV_AMD_CHAINM_ABL sets the f32m chain's ablation bits (TdnnChainParams::abl), the garbage-result ones only under
+          // ASV_AMD_CHAIN_DBG
+          static const bool chainm_group_off = getenv("ASV_AMD_CHAINM_GROUP") != nullptr && atoi(getenv("ASV_AMD_CHAINM_GROUP")) == 0;
+          if (cp.x_image && chainm_group_off) cp.x_image = 2;
+          static const int chainm_abl = getenv("ASV_AMD_CHAINM_ABL") != nullptr ? atoi(getenv("ASV_AMD_CHAINM_ABL")) : 0;       // read once
+          cp.abl = (chainm_abl & ~8) != 0 && getenv("ASV_AMD_CHAIN_DBG") == nullptr ? (chainm_abl & 8) : chainm_abl;
+#endif
+          cp.n128 = ch.plan.n128; cp.n_tail = ch.plan.n_tail; cp.tail_rows = ch.plan.tail_rows;
+          if ((rc = ensure(net->poolpart_dev, (size_t)ch.n_blocks * ch.pool_slots * 2 * 3 * cp.ld_partial * 4, c.s, false))) return rc;
+          cp.pool_partial = reinterpret_cast<float *>(net->poolpart_dev.ptr);
+          double fl = 0.0;
+          for (size_t k = i; k <= l; ++k) fl += 2.0 * (double)bp.frames * net->ops[k].tdnn.in_ch * net->ops[k].tdnn.out_ch * net->ops[k].tdnn.n_taps;
+          if ((rc = prof.begin(K_TDNN, fl, (int)i))) return rc;
+          // developer aid (ASV_AMD_CHAIN_DBG): phase stamps of the 16-bit and the f32m chain, one block of 8 x 32 per workgroup
+          const bool stamps = c.rules.chain_dbg != 0 && ch.path != TdnnPath::ChainX;
+          const size_t n_wgs = (size_t)(p.rows / (ch.path == TdnnPath::ChainM ? 64 : 128));
+          DevMem dbg;
+          if (stamps) {
+            if ((rc = ensure(dbg, n_wgs * 8 * 32 * 8, c.s, true))) return rc;
+            cp.dbg = reinterpret_cast<unsigned long long *>(dbg.ptr);
+            cp.dbg_fine = c.rules.chain_dbg >= 3;
           }
-          if (slots <= 16) {
-            ASV_REQUIRE(!p.x_image || (chain_mx && !mx96), "tdnn(chain): image rows reached a chain kernel that cannot read them (internal)");
-            const size_t l = (size_t)op.chain_last;
-            Op &lo = net->ops[l];
-            TdnnChainParams cp;
-            memset(&cp, 0, sizeof(cp));
-            cp.x = p.x; cp.ldx = p.ldx; cp.rows = p.rows; cp.cin_pad = p.cin_pad; cp.n_taps = p.n_taps;
-            for (int t = 0; t < p.n_taps; ++t) cp.taps[t] = p.taps[t];
-            // a layer whose consumer holds folded weights (wfrag_fold) stores ReLU(acc) only: its scale / shift are not passed
-            auto layer_of = [&](size_t k) {
-              const Op &o = net->ops[k];
-              const bool folded_in = o.wfrag_fold != nullptr;                                  // the previous layer's BN sits in these weights
-              const bool folded_out = k < l && net->ops[k + 1].wfrag_fold != nullptr;          // this layer's BN sits in the next layer's
-              TdnnChainLayer L;
-              L.wfrag = folded_in ? o.wfrag_fold : o.wfrag; L.bias = folded_in ? o.bias_fold : o.bias;
-              L.wlo = folded_in ? o.wlo_fold : o.wlo; L.w_scale = folded_in ? o.w_scale_fold : o.w_scale;
-              L.w8 = folded_in ? o.w8_fold : o.w8;
-              L.scale = folded_out ? nullptr : o.scale; L.shift = folded_out ? nullptr : o.shift;
-              L.relu = o.tdnn.act1 == ASV_ACT_RELU; L.cout_pad = o.cout_pad;
-              return L;
-            };
-            cp.first = layer_of(i);
-            cp.n_mid = (int)(l - i - 1);
-            for (size_t k = i + 1; k < l; ++k) cp.mid[k - i - 1] = layer_of(k);
-            cp.last = layer_of(l);
-            cp.pool_slots = slots; cp.ld_partial = lo.cout_pad; cp.row_seg = dr.row_seg;
-            cp.et = chain_x3 ? net->x3_et() : et;
-            cp.min_seg_len = min_len;
-            cp.status = status_word(net);
-            static const bool chainm_group_off = getenv("ASV_AMD_CHAINM_GROUP") != nullptr && atoi(getenv("ASV_AMD_CHAINM_GROUP")) == 0;      // measuring aid (same results)
-            cp.x_image = p.x_image ? (chainm_group_off ? 2 : 1) : 0;
-            static const int chainm_abl = getenv("ASV_AMD_CHAINM_ABL") != nullptr ? atoi(getenv("ASV_AMD_CHAINM_ABL")) : 0;       // developer aid, read once
-            cp.abl = (chainm_abl & ~8) != 0 && getenv("ASV_AMD_CHAIN_DBG") == nullptr ? (chainm_abl & 8) : chainm_abl;               // the garbage-result bits only under ASV_AMD_CHAIN_DBG
-            cp.n128 = plan.n128; cp.n_tail = plan.n_tail; cp.tail_rows = plan.tail_rows;
-            if ((rc = ensure(net->poolpart_dev, (size_t)n_blocks * slots * 2 * 3 * cp.ld_partial * 4, c.s, false))) return rc;
-            cp.pool_partial = reinterpret_cast<float *>(net->poolpart_dev.ptr);
-            double fl = 0.0;
-            for (size_t k = i; k <= l; ++k) fl += 2.0 * (double)bp.frames * net->ops[k].tdnn.in_ch * net->ops[k].tdnn.out_ch * net->ops[k].tdnn.n_taps;
-            if ((rc = prof.begin(K_TDNN, fl, (int)i))) return rc;
-            static const int chain_dbg = getenv("ASV_AMD_CHAIN_DBG") != nullptr ? std::max(1, atoi(getenv("ASV_AMD_CHAIN_DBG"))) : 0;   // developer aid: phase durations to stderr
-            DevMem dbg;
-            const size_t dbg_wgs = mx96 ? (size_t)n_blocks : (chain_mx ? (size_t)(p.rows / 64) : (size_t)(p.rows / 128));
-            if (chain_dbg && (!chain_x3 || chain_mx)) {
-              if ((rc = ensure(dbg, dbg_wgs * 8 * 32 * 8, c.s, true))) return rc;
-              cp.dbg = reinterpret_cast<unsigned long long *>(dbg.ptr);
-              cp.dbg_fine = chain_dbg >= 3;
-
-            }
-            if (chain_mx) ++g_kernel_launches[ASV_KERNEL_TDNN_CHAINM];
-            if ((rc = mx96 ? launch_tdnn_chainm96(cp, c.s) : (chain_mx ? launch_tdnn_chainm(cp, c.s) : (chain_x3 ? launch_tdnn_chainx(cp, c.s) : launch_tdnn_chain(cp, c.s))))) return rc;
-            if ((rc = prof.end())) return rc;
-            if (chain_dbg && (!chain_x3 || chain_mx)) {
-              const size_t nwg = dbg_wgs;
-              std::vector<unsigned long long> h(nwg * 8 * 32);
-              ASV_HIP_CHECK(hipStreamSynchronize(c.s));
-              ASV_HIP_CHECK(hipMemcpy(h.data(), dbg.ptr, h.size() * 8, hipMemcpyDeviceToHost));
-              ASV_HIP_CHECK(hipFree(dbg.ptr));
-              double sum[32] = {0}; size_t cnt = 0; double cyc = 0, rt = 0;
-              for (size_t w = 0; w < nwg * 8; ++w) {
-                const unsigned long long *t = &h[w * 32];
-                if (t[0] == 0) continue;
-                for (int k = 1; k < 14; ++k) if (t[k] > t[k - 1]) sum[k] += (double)(t[k] - t[k - 1]);      // 13: the 4-wave kernel's drain
-                if (chain_dbg >= 3) {
-                  if (t[16] > t[7]) sum[16] += (double)(t[16] - t[7]);                                   // unit's K loop end -> epilogue body
-                  for (int k = 17; k < 22; ++k) if (t[k] > t[k - 1]) sum[k] += (double)(t[k] - t[k - 1]);
-                }
-                const unsigned long long t_end = t[13] > t[12] ? t[13] : t[12];
-                if (t_end > t[0] && t[15] > t[14]) { cyc += (double)(t_end - t[0]); rt += (double)(t[15] - t[14]); }
-                ++cnt;
-              }
-              fprintf(stderr, "[chain dbg] %zu waves, mean cycles per phase:", cnt);
-              fprintf(stderr, " [shader clock %.0f MHz, %.1f us per workgroup]", rt > 0 ? 100.0 * cyc / rt : 0.0, cnt ? rt / 100.0 / (double)cnt : 0.0);
-              for (int k = 1; k < 14; ++k) if (k < 13 || sum[k] > 0) fprintf(stderr, " %d:%.0f", k, sum[k] / (double)std::max<size_t>(cnt, 1));
-              if (chain_dbg >= 3) {
-                fprintf(stderr, " | first epilogue: entry %.0f, fragments", sum[16] / (double)std::max<size_t>(cnt, 1));
-                for (int k = 17; k < 21; ++k) fprintf(stderr, " %.0f", sum[k] / (double)std::max<size_t>(cnt, 1));
-                fprintf(stderr, ", publish %.0f", sum[21] / (double)std::max<size_t>(cnt, 1));
-              }
-              fprintf(stderr, "\n");
-              if (chain_mx && chain_dbg >= 3) {                      // layer A, steps 0 .. 14: mean cycles per step, by wave
-                for (int wv = 0; wv < 8; ++wv) {
-                  double d[15] = {0}; size_t cn = 0;
-                  for (size_t wg = 0; wg < nwg; ++wg) {
-                    const unsigned long long *t = &h[(wg * 8 + wv) * 32];
-                    if (t[16] == 0 || t[31] <= t[16]) continue;
-                    for (int k = 0; k < 15; ++k) d[k] += (double)(t[17 + k] - t[16 + k]);
-                    ++cn;
-                  }
-                  fprintf(stderr, "[chainm dbg] wave %d, cycles of layer A's steps 0..14:", wv);
-                  for (int k = 0; k < 15; ++k) fprintf(stderr, " %.0f", d[k] / (double)std::max<size_t>(cn, 1));
-                  fprintf(stderr, "\n");
-                }
-              }
-              {                                                       // 4-wave kernel, ablation 8: fine stamps of wave 0's third unit (slots of wave 4..7)
-                double fs[25] = {0}; size_t fc = 0;
-                for (size_t wg = 0; wg < nwg; ++wg) {
-                  const unsigned long long *t = &h[(wg * 8 + 4) * 32];
-                  if (t[0] == 0 || t[24] <= t[0]) continue;
-                  for (int k = 1; k < 25; ++k) fs[k] += (double)(t[k] - t[k - 1]);
-                  ++fc;
-                }
-                if (fc) {
-                  fprintf(stderr, "[chain dbg] third unit of wave 0, %zu workgroups, per chunk: pre | 32 matrix instructions | post:", fc);
-                  for (int c = 0; c < 8; ++c) fprintf(stderr, "  %.0f | %.0f | %.0f", fs[3 * c + 1] / fc, fs[3 * c + 2] / fc, fs[3 * c + 3] / fc);
-                  fprintf(stderr, "\n");
-                }
-              }
-              if (chain_dbg == 2 || chain_dbg >= 4) {                 // raw timelines of two workgroups: waves w and w + 4 share a SIMD
-                const size_t picks[2] = {nwg / 4, nwg / 2 + 1};
-                for (size_t wg : picks) {
-                  if (wg >= nwg) continue;
-                  unsigned long long t0 = ~0ull;
-                  for (int w = 0; w < 8; ++w) if (h[(wg * 8 + w) * 32] != 0) t0 = std::min(t0, h[(wg * 8 + w) * 32]);
-                  for (int w = 0; w < 8; ++w) {
-                    fprintf(stderr, "[chain dbg] workgroup %zu wave %d stamps (cycles since the first wave's stamp 0):", wg, w);
-                    for (int k = 0; k < 13; ++k) fprintf(stderr, " %lld", (long long)(h[(wg * 8 + w) * 32 + k] - t0));
-                    if (chain_dbg >= 4) { fprintf(stderr, " |"); for (int k = 16; k < 22; ++k) fprintf(stderr, " %lld", (long long)(h[(wg * 8 + w) * 32 + k] - t0)); }
-                    fprintf(stderr, "\n");
-                  }
-                }
-              }
-            }
-            Op &po = net->ops[lo.fused_pool];
-            po.skipped = true;
-            const auto &q = po.pool;
-            PoolFinishParams f;
-            f.partial = cp.pool_partial; f.ld_partial = cp.ld_partial; f.pool_slots = slots; f.lh_split = 1; f.tile_shift = tshift;
-            f.rows_shift = plan.rows128(); f.tail_rows = plan.n_tail > 0 ? plan.tail_rows : 0; f.n_shift = plan.n128;
-            if (mx96) { f.rows_shift = 0; f.tail_rows = 96; f.n_shift = 0; }       // uniform 96-row blocks (pool_finish_kernel's tail form from row 0 on)
-            f.row_seg = dr.row_seg; f.rows = dr.rows_pad; f.seg_row0 = dr.seg_row0; f.seg_len = dr.seg_len;
-            f.shift = lo.shift;
-            f.out = reinterpret_cast<float *>(net->arena[q.out_buf].ptr) + q.out_ch_off; f.ld_out = net->bufs[q.out_buf].ld; f.channels = q.channels;
-            f.stddev = q.stddev; f.unbiased = q.unbiased; f.var_mode = q.var_mode; f.eps = q.eps;
-            if ((rc = prof.begin(K_POOL, 0, lo.fused_pool))) return rc;
-            if ((rc = launch_pool_finish(f, bp.segments, c.s))) return rc;
-            if ((rc = prof.end())) return rc;
-            i = l;                                       // the chain's other layers ran inside the kernel
-            break;
-          }
-        }
-        const bool narrow = p.halo <= kHalo;
-        // fused statistics pooling: needs few enough segments per 128-row half-tile (i.e. no tiny utterances)
-        int pool_slots = 0;
-        if (op.fused_pool >= 0 && !use_ref && (net->flags & ASV_FLAG_SMALL_TILES) == 0) {
-          const DomainPlan &fp = bp.dom[ASV_DOMAIN_FRAMES];
-          std::vector<int> per_half((size_t)fp.rows_pad / 128 + 1, 0);
-          int worst = 1;
-          for (size_t sidx = 0; sidx < fp.seg_row0.size(); ++sidx)
-            for (int h = fp.seg_row0[sidx] >> 7; h <= (fp.seg_row0[sidx] + fp.seg_len[sidx] - 1) >> 7; ++h) worst = std::max(worst, ++per_half[h]);
-          pool_slots = worst;
-          if (pool_slots > 16) pool_slots = 0;               // many tiny utterances: use the separate pooling kernel
-        }
-        const bool big3 = !use_ref && narrow && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && tdnn_big3_supported(p, et, !bf16);
-        const bool utts_kernel = !use_ref && op.utts;
-        const bool x3 = x3_rule(op, p);
-        const bool c1_conv = !use_ref && net->domains[domid].kind == 2 && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && grid_conv_c1_supported(p, et, d.in_ch);
-        const bool narrow_conv = !use_ref && net->domains[domid].kind == 2 && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && grid_conv_narrow_supported(p, et);
-        const bool wide_conv = !use_ref && net->domains[domid].kind == 2 && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && grid_conv_wide_supported(p, et);
-        const bool s2d_conv = !use_ref && net->domains[domid].kind == 2 && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && grid_conv_s2d_supported(p, et);
-        const bool x3_conv = !use_ref && !op.utts && net->x3() && !x3 && (net->flags & ASV_FLAG_SMALL_TILES) == 0 && grid_conv_x3_supported(p);
-        if (!use_ref && !big3 && op.utts && !utts_kernel) {
-          // pooled-domain layers have one row per utterance (M is tiny, K is large): slice K over more
-          // workgroups.  The slice count depends on K only, never on the batch, so an utterance's
-          // embedding is bit-identical whatever batch it is extracted in.
-          const int nchunks = (p.cin_pad + (bf16 ? 64 : 32) - 1) / (bf16 ? 64 : 32);
-          p.ksplit = std::min(nchunks / 4, 24);
-          if (p.ksplit > 1) {
-            p.ld_partial = round_up(p.cout_store, 64);
-            if ((rc = ensure(net->splitk_dev, (size_t)p.ksplit * p.rows * p.ld_partial * 4, c.s, false))) return rc;
-            p.partial = reinterpret_cast<float *>(net->splitk_dev.ptr);
-          } else {
-            p.ksplit = 0;
-          }
+          if (ch.path == TdnnPath::ChainM) ++g_kernel_launches[ASV_KERNEL_TDNN_CHAINM];
+          if ((rc = ch.path == TdnnPath::ChainM ? launch_tdnn_chainm(cp, c.s) : (ch.path == TdnnPath::ChainX ? launch_tdnn_chainx(cp, c.s) : launch_tdnn_chain(cp, c.s)))) return rc;
+          if ((rc = prof.end())) return rc;
+          if (stamps && (rc = report_chain_stamps(dbg.ptr, n_wgs, c.rules.chain_dbg, ch.path == TdnnPath::ChainM, c.s))) return rc;
+          net->ops[lo.fused_pool].skipped = true;
+          if ((rc = finish_fused_pool(c, prof, lo.fused_pool, dr, cp.pool_partial, cp.ld_partial, ch.pool_slots, 1, ch.path == TdnnPath::Chain16 ? 7 : 6,
+                                      ch.plan, lo.shift))) return rc;
+          i = l;                                       // the chain's other layers ran inside the kernel
+          break;
         }
         double valid_rows = op.utts ? (double)bp.segments : (double)bp.frames;
         if (net->domains[domid].kind == 2) {
@@ -1586,75 +1614,51 @@ int run_ops(RunCtx &c, size_t n_ops) {
           for (int32_t len : bp.dom[domid].seg_len) valid_rows += (double)(len / net->domains[domid].pitch) * net->domains[domid].width;
         }
         if ((rc = prof.begin(op.utts ? K_UTTS : K_TDNN, 2.0 * valid_rows * d.in_ch * d.out_ch * d.n_taps * (d.alg_fraction > 0.0f ? (double)d.alg_fraction : 1.0), (int)i))) return rc;
-        const bool fuse = pool_slots > 0 && (big3 || (x3 && tdnn_x3_pool_supported(p)));
-        if (fuse) {
-          p.pool_slots = pool_slots;
+        if (ch.pool_slots > 0) {
+          p.pool_slots = ch.pool_slots;
           p.ld_partial = op.cout_pad;
-          if ((rc = ensure(net->poolpart_dev, (size_t)(p.rows / 128) * pool_slots * 3 * p.ld_partial * 4, c.s, false))) return rc;
+          if ((rc = ensure(net->poolpart_dev, (size_t)(p.rows / 128) * ch.pool_slots * 3 * p.ld_partial * 4, c.s, false))) return rc;
           p.pool_partial = reinterpret_cast<float *>(net->poolpart_dev.ptr);
         }
-        // Round 5: the layers of the variant-3 kernel with the plain epilogue, whole 64-channel chunks and at least one round of 256 x 256
-        // tiles on the chip's CUs go to the 8-phase kernel (kernels_tdnn_p8.hip: both operands through LDS-DMA, staggered wave rows;
-        // bit-identical outputs, 1.03 - 1.15 x the rate: profiles/r5e_p8_shapes.txt).  ASV_AMD_P8=0: the variant-3 kernel everywhere.
-        const bool p8 = big3 && !fuse && p8_on != 0 && tdnn_p8_supported(p, et, !bf16) &&
-                        (long long)(p.rows / 256) * (round_up(p.cout_store, 256) / 256) >= (p8_on > 1 ? p8_on : cus);
-        // ... and the f32x / f32m forms (the rules: p8x_rule, x3m_rule above)
-        const bool p8x = p8x_rule(p, x3, fuse);
-        const bool x3m = x3m_rule(p, x3, fuse);
-        ASV_REQUIRE(!p.x_image || (x3m && tdnn_x3m_image_in_supported(p)), "tdnn: image rows reached a kernel that cannot read them (internal)");
+        ASV_REQUIRE(!p.x_image || (ch.path == TdnnPath::X3m && tdnn_x3m_image_in_supported(p)), "tdnn: image rows reached a kernel that cannot read them (internal)");
         // f32m: the output rows as images, when their one reader will take them as such in this run (Op::image_reader; ASV_AMD_X3M_IMAGE=0: off)
-        if (x3m && img_on != 0 && op.image_reader >= 0 && (size_t)op.image_reader < n_ops && tdnn_x3m_image_out_supported(p) &&
+        if (ch.path == TdnnPath::X3m && c.rules.x3m_image != 0 && op.image_reader >= 0 && (size_t)op.image_reader < n_ops && tdnn_x3m_image_out_supported(p) &&
             reader_takes_image((size_t)op.image_reader)) {
           p.y_image = 1;
           c.buf_image[d.out_buf] = 1;
           ++g_kernel_launches[ASV_KERNEL_TDNN_X3M_IMAGE];
         }
-        if (use_ref) rc = launch_tdnn_ref(p, et, !bf16, c.s);
-        else if (utts_kernel) {
-          // last layer, every utterance a single chunk: the kernel also produces the caller's [utterance][embed_dim] result
-          if (c.final_out != nullptr && i + 1 == net->ops.size() && d.out_buf == net->out_buf && d.out_ch_off == 0 && d.out_ch == net->embed_dim &&
-              bp.segments == bp.n_utts) {
-            p.final_out = c.final_out; p.final_ld = net->embed_dim; p.final_len = c.seg_frames;
-            c.final_written = true;
-          }
-          // pooled-domain layers: split-bf16 products (f32-grade to ~2^-17, twice the rate of the f32-input MFMA) in the 16-bit
-          // throughput modes; the exact f32-input MFMA in the parity modes - with IEEE-half operand halves in the frame layers
-          // the bf16 split here would be the largest error left in the f32x mode (< 0.3 % of the FLOPs: +1 % of an f32x step)
-          rc = launch_utts_gemm(p, bp.segments, net->frames_h16(), c.s);
-        }
-        else if (narrow_conv) rc = launch_grid_conv_narrow(p, c.s);
-        else if (wide_conv) rc = launch_grid_conv_wide(p, c.s);
-        else if (s2d_conv) rc = launch_grid_conv_s2d(p, c.s);
-        else if (c1_conv) rc = launch_grid_conv_c1(p, c.s);
-        else if (x3m) { rc = launch_tdnn_x3m(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_X3M]; }
-        else if (p8x) { rc = launch_tdnn_p8x(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_P8X]; }
-        else if (x3) rc = launch_tdnn_x3(p, c.s);
-        else if (x3_conv) rc = launch_grid_conv_x3(p, c.s);
-        else if (p8) { rc = launch_tdnn_p8(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_P8]; }
-        else if (big3) { rc = launch_tdnn_big3(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_BIG3]; }
-        else {
-          rc = launch_tdnn_mfma(p, et, !bf16, c.s);
-          if (!rc && p.ksplit > 1) rc = launch_splitk_epilogue(p, et, !bf16, c.s);
+        switch (ch.path) {
+          case TdnnPath::Ref: rc = launch_tdnn_ref(p, et, !h16, c.s); break;
+          case TdnnPath::Utts:
+            // last layer, every utterance a single chunk: the kernel also produces the caller's [utterance][embed_dim] result
+            if (c.final_out != nullptr && i + 1 == net->ops.size() && d.out_buf == net->out_buf && d.out_ch_off == 0 && d.out_ch == net->embed_dim &&
+                bp.segments == bp.n_utts) {
+              p.final_out = c.final_out; p.final_ld = net->embed_dim; p.final_len = c.seg_frames;
+              c.final_written = true;
+            }
+            // pooled-domain layers: split-bf16 products (f32-grade to ~2^-17, twice the rate of the f32-input MFMA) in the 16-bit
+            // throughput modes; the exact f32-input MFMA in the parity modes - with IEEE-half operand halves in the frame layers
+            // the bf16 split here would be the largest error left in the f32x mode (< 0.3 % of the FLOPs: +1 % of an f32x step)
+            rc = launch_utts_gemm(p, bp.segments, net->frames_h16(), c.s);
+            break;
+          case TdnnPath::ConvNarrow: rc = launch_grid_conv_narrow(p, c.s); break;
+          case TdnnPath::ConvWide: rc = launch_grid_conv_wide(p, c.s); break;
+          case TdnnPath::ConvS2d: rc = launch_grid_conv_s2d(p, c.s); break;
+          case TdnnPath::ConvC1: rc = launch_grid_conv_c1(p, c.s); break;
+          case TdnnPath::X3m: rc = launch_tdnn_x3m(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_X3M]; break;
+          case TdnnPath::P8x: rc = launch_tdnn_p8x(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_P8X]; break;
+          case TdnnPath::X3: rc = launch_tdnn_x3(p, c.s); break;
+          case TdnnPath::ConvX3: rc = launch_grid_conv_x3(p, c.s); break;
+          case TdnnPath::P8: rc = launch_tdnn_p8(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_P8]; break;
+          case TdnnPath::Big3: rc = launch_tdnn_big3(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_BIG3]; break;
+          default: rc = launch_tdnn_mfma(p, et, !h16, c.s); break;              // TdnnPath::Mfma (the chains were launched above)
         }
         if (rc) return rc;
         if ((rc = prof.end())) return rc;
-        if (op.fused_pool >= 0) {
-          Op &po = net->ops[op.fused_pool];
-          po.skipped = fuse;
-          if (fuse) {
-            const auto &q = po.pool;
-            PoolFinishParams f;
-            f.partial = p.pool_partial; f.ld_partial = p.ld_partial; f.pool_slots = pool_slots; f.lh_split = 0; f.tile_shift = 7;
-            f.rows_shift = 0; f.tail_rows = 0; f.n_shift = 0;
-            f.row_seg = dr.row_seg; f.rows = dr.rows_pad; f.seg_row0 = dr.seg_row0; f.seg_len = dr.seg_len;
-            f.shift = op.shift;
-            f.out = reinterpret_cast<float *>(net->arena[q.out_buf].ptr) + q.out_ch_off; f.ld_out = net->bufs[q.out_buf].ld; f.channels = q.channels;
-            f.stddev = q.stddev; f.unbiased = q.unbiased; f.var_mode = q.var_mode; f.eps = q.eps;
-            if ((rc = prof.begin(K_POOL, 0, op.fused_pool))) return rc;
-            if ((rc = launch_pool_finish(f, bp.segments, c.s))) return rc;
-            if ((rc = prof.end())) return rc;
-          }
-        }
+        if (op.fused_pool >= 0) net->ops[op.fused_pool].skipped = ch.pool_slots > 0;
+        if (ch.pool_slots > 0 &&
+            (rc = finish_fused_pool(c, prof, op.fused_pool, dr, p.pool_partial, p.ld_partial, ch.pool_slots, 0, 7, ChainTilePlan(), op.shift))) return rc;
         break;
       }
       case OP_POOL: {
