@@ -285,6 +285,16 @@ int launch_attentive_pool(const void *x, int ldx, const void *logits, int ldl, i
                           const int32_t *seg_row0, const int32_t *seg_len, int segments, float eps,
                           float *out, int ld_out, int et, int group, int softplus2, const float *prior_logit, const float *prior_value,
                           hipStream_t s);
+// multi-query multi-head attentive pooling (mq_attentive_pool_kernel): pair p = head * queries + query of channel c = head * head_ch + j
+// reads logit column p (shared) or p * head_ch + j and writes mean to out[p * pair_stride + j], std to out[p * pair_stride + std_off + j]
+struct MqPoolKernelParams {
+  const void *x, *logits; int ldx, ldl;
+  int channels, head_ch;                 // channels = heads * head_ch; head_ch is a multiple of 16
+  const int32_t *seg_row0, *seg_len;
+  float eps;
+  float *out; int ld_out, pair_stride, std_off;
+};
+int launch_mq_attentive_pool(const MqPoolKernelParams &p, int queries, int shared, int segments, int et, hipStream_t s);   // queries: 1 .. 4
 // row r of a segment is valid iff (r - row0) % pitch < width (frames domain: pitch = width = 1)
 int launch_rowmap(const int32_t *seg_row0, const int32_t *seg_len, int segments, int rows, int pitch, int width,
                   int32_t *row_seg, uint32_t *row_valid, hipStream_t s);

@@ -463,6 +463,150 @@ __global__ __launch_bounds__(256) void attentive_pool_kernel(const void *x, int 
   }
 }
 
+// Multi-query multi-head attentive statistics (libs/nnet/pooling.py:590-701, MQMHASP): the channels form heads of `head_ch`, every
+// head is pooled Q times, pair p = head * Q + query with logit column p (SHARED: one per frame) or columns [p head_ch, (p + 1) head_ch).
+// One launch instead of heads x Q launches of attentive_pool_kernel on head views, and every x row is read ONCE for its Q weightings.
+// The thread-to-(row, channel) mapping, the two paths and every accumulation statement are attentive_pool_kernel's, per query: each
+// (channel, query) sum is formed from the same operands in the same order as in the separate launch, so the results are the same bits.
+// A workgroup's 64 channels may span two heads (head_ch is a multiple of 16, a lane's VEC channels never do).
+template <int ET, int Q, bool SHARED>
+__global__ __launch_bounds__(256) void mq_attentive_pool_kernel(const MqPoolKernelParams p) {
+  constexpr int VEC = (ET != ET_F32) ? 8 : 4;
+  constexpr int CG = 64 / VEC;
+  constexpr int RS = 64 / CG;
+  __shared__ float sm[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cg = lane % CG, rs = lane / CG;
+  const int seg = blockIdx.y, ch = blockIdx.x * 64 + cg * VEC;
+  const int row0 = p.seg_row0[seg], len = p.seg_len[seg];
+  const bool active = ch < p.channels;                        // channels = heads * head_ch, a multiple of 16
+  const int head = active ? ch / p.head_ch : 0, cl = active ? ch - head * p.head_ch : 0;
+  const void *x = p.x, *logits = p.logits;
+  const int ldx = p.ldx, ldl = p.ldl;
+
+  auto load_logits = [&](int r, int q, float (&e)[VEC]) {
+    if constexpr (SHARED) {
+      const float e0 = load_elem<ET>(logits, (size_t)(row0 + r) * ldl + head * Q + q);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) e[i] = e0;
+    } else {
+      load_vec<ET, VEC>(logits, (size_t)(row0 + r) * ldl + (size_t)(head * Q + q) * p.head_ch + cl, e);
+    }
+  };
+  float mx[Q][VEC], se[Q][VEC], sx[Q][VEC], sxx[Q][VEC];
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { mx[q][i] = -INFINITY; se[q][i] = 0.0f; sx[q][i] = 0.0f; sxx[q][i] = 0.0f; }
+  if constexpr (ET != ET_F32) {
+    // throughput mode: one pass, running maxima per lane and query (see attentive_pool_kernel)
+    float lm[Q][VEC];
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) lm[q][i] = -INFINITY;
+    if (active) {
+      int r = wave * RS + rs;
+      for (; r + 4 * RS < len; r += 8 * RS) {
+        float v0[VEC], v1[VEC];
+        load_vec<ET, VEC>(x, (size_t)(row0 + r) * ldx + ch, v0);
+        load_vec<ET, VEC>(x, (size_t)(row0 + r + 4 * RS) * ldx + ch, v1);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          float e0[VEC], e1[VEC];
+          load_logits(r, q, e0);
+          load_logits(r + 4 * RS, q, e1);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            const float mn = fmaxf(lm[q][i], fmaxf(e0[i], e1[i]));
+            const float sc = __expf(lm[q][i] - mn), w0 = __expf(e0[i] - mn), w1 = __expf(e1[i] - mn);
+            se[q][i] = fmaf(se[q][i], sc, w0 + w1);
+            sx[q][i] = fmaf(sx[q][i], sc, fmaf(w0, v0[i], w1 * v1[i]));
+            sxx[q][i] = fmaf(sxx[q][i], sc, fmaf(w0 * v0[i], v0[i], w1 * v1[i] * v1[i]));
+            lm[q][i] = mn;
+          }
+        }
+      }
+      for (; r < len; r += 4 * RS) {
+        float v[VEC];
+        load_vec<ET, VEC>(x, (size_t)(row0 + r) * ldx + ch, v);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          float e[VEC];
+          load_logits(r, q, e);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            const float mn = fmaxf(lm[q][i], e[i]);
+            const float sc = __expf(lm[q][i] - mn), w = __expf(e[i] - mn);
+            se[q][i] = fmaf(se[q][i], sc, w);
+            sx[q][i] = fmaf(sx[q][i], sc, w * v[i]);
+            sxx[q][i] = fmaf(sxx[q][i], sc, w * v[i] * v[i]);
+            lm[q][i] = mn;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) mx[q][i] = lm[q][i];
+      block_max_rows<VEC, CG>(mx[q], sm, wave, cg, rs);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const float f = lm[q][i] == -INFINITY ? 0.0f : __expf(lm[q][i] - mx[q][i]);
+        se[q][i] *= f; sx[q][i] *= f; sxx[q][i] *= f;
+      }
+    }
+  } else {
+    // parity modes: the maxima of all Q logit sets first, then ONE pass over x with libm exponentials
+    if (active)
+      for (int r = wave * RS + rs; r < len; r += 4 * RS) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          float e[VEC];
+          load_logits(r, q, e);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) mx[q][i] = fmaxf(mx[q][i], e[i]);
+        }
+      }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) block_max_rows<VEC, CG>(mx[q], sm, wave, cg, rs);
+    if (active)
+      for (int r = wave * RS + rs; r < len; r += 4 * RS) {
+        float v[VEC];
+        load_vec<ET, VEC>(x, (size_t)(row0 + r) * ldx + ch, v);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          float e[VEC];
+          load_logits(r, q, e);
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            const float w = expf(e[i] - mx[q][i]);
+            se[q][i] += w; sx[q][i] += w * v[i]; sxx[q][i] += w * v[i] * v[i];
+          }
+        }
+      }
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    block_reduce_rows<VEC, CG>(se[q], sm, wave, cg, rs);
+    block_reduce_rows<VEC, CG>(sx[q], sm, wave, cg, rs);
+    block_reduce_rows<VEC, CG>(sxx[q], sm, wave, cg, rs);
+    if (wave == 0 && rs == 0 && active) {
+      float *dst = p.out + (size_t)seg * p.ld_out + (size_t)(head * Q + q) * p.pair_stride + cl;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const float mean = sx[q][i] / se[q][i];
+        float m2 = mean * mean;
+        asm volatile("" : "+v"(m2));                            // no fma contraction (see attentive_pool_kernel)
+        const float resid = sxx[q][i] / se[q][i] - m2;
+        dst[i] = mean;
+        dst[p.std_off + i] = sqrtf(fmaxf(resid, p.eps));
+      }
+    }
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------
 // Learnable dictionary encoding pooling (libs/nnet/pooling.py:130-162).
@@ -888,6 +1032,25 @@ int launch_attentive_pool(const void *x, int ldx, const void *logits, int ldl, i
   return ASV_OK;
 }
 
+int launch_mq_attentive_pool(const MqPoolKernelParams &p, int queries, int shared, int segments, int et, hipStream_t s) {
+  if (segments <= 0) return ASV_OK;
+  ASV_REQUIRE(queries >= 1 && queries <= 4, "multi-query attentive pooling: %d queries (the kernel exists for 1 .. 4)", queries);
+  const dim3 grid((p.channels + 63) / 64, segments), block(256);
+#define ASV_MQ_ET(QN, SH) do { if (et == ET_BF16) hipLaunchKernelGGL((mq_attentive_pool_kernel<ET_BF16, QN, SH>), grid, block, 0, s, p); \
+                               else if (et == ET_F16) hipLaunchKernelGGL((mq_attentive_pool_kernel<ET_F16, QN, SH>), grid, block, 0, s, p); \
+                               else hipLaunchKernelGGL((mq_attentive_pool_kernel<ET_F32, QN, SH>), grid, block, 0, s, p); } while (0)
+#define ASV_MQ_Q(QN) do { if (shared) ASV_MQ_ET(QN, true); else ASV_MQ_ET(QN, false); } while (0)
+  switch (queries) {
+    case 1: ASV_MQ_Q(1); break;
+    case 2: ASV_MQ_Q(2); break;
+    case 3: ASV_MQ_Q(3); break;
+    default: ASV_MQ_Q(4); break;
+  }
+#undef ASV_MQ_Q
+#undef ASV_MQ_ET
+  ASV_HIP_CHECK(hipGetLastError());
+  return ASV_OK;
+}
 
 int launch_lde_pool(const void *x, int ldx, int channels, int rows, const float *mu, const float *beta, int n_centres, float *weights,
                     const int32_t *seg_row0, const int32_t *seg_len, int segments, float *out, int ld_out, int et, hipStream_t s) {

@@ -156,7 +156,7 @@ struct Domain {
   int gap() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : pitch + 2; }
 };
 
-enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8 };
+enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9 };
 
 struct Op {
   OpKind kind;
@@ -169,6 +169,7 @@ struct Op {
   asv_im2col_desc_t i2c;
   asv_grid_flatten_desc_t flat;
   asv_lde_desc_t lde;            // mu / beta live in `scale` / `shift` on the device
+  asv_mq_attpool_desc_t mq;
   asv_res2_desc_t res2;          // fragments in `wfrag`, per-branch constants in bias / scale / shift
   // device parameters
   void *w = nullptr;
@@ -259,7 +260,7 @@ struct asv_net {
 
 namespace {
 
-std::atomic<unsigned long long> g_kernel_launches[7];       // asv_kernel_launch_count
+std::atomic<unsigned long long> g_kernel_launches[8];       // asv_kernel_launch_count
 
 // the range-status word of the f32x kernels lives behind the zero page's zeros (own 64-byte line; kernels only ever OR into it)
 uint32_t *status_word(asv_net *net) { return reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(net->zero_page) + 128); }
@@ -708,6 +709,33 @@ int asv_net_add_attentive_pool(asv_net_t *net, const asv_attpool_desc_t *d) {
   return ASV_OK;
 }
 
+int asv_net_add_mq_attentive_pool(asv_net_t *net, const asv_mq_attpool_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_mq_attentive_pool: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_mq_attpool_desc_t), "asv_net_add_mq_attentive_pool: struct_size mismatch");
+  ASV_REQUIRE(d->heads >= 1 && d->queries >= 1 && d->queries <= 4, "mq attentive pool: %d heads, %d queries (1 .. 4 queries)", d->heads, d->queries);
+  ASV_REQUIRE(d->channels >= 1 && d->channels % d->heads == 0 && (d->channels / d->heads) % kChanAlign == 0,
+              "mq attentive pool: %d channels in %d heads: every head needs a multiple of %d channels", d->channels, d->heads, kChanAlign);
+  const int head_ch = d->channels / d->heads, pairs = d->heads * d->queries;
+  int rc;
+  if ((rc = check_view(net, d->x_buf, d->x_ch_off, d->channels, "mq attentive pool x"))) return rc;
+  if (d->shared_logits) {          // one element per (frame, pair): any column offset, like the head logits of asv_attpool_desc_t
+    ASV_REQUIRE(d->logit_buf >= 0 && d->logit_buf < (int)net->bufs.size() && d->logit_ch_off >= 0 && d->logit_ch_off + pairs <= net->bufs[d->logit_buf].channels,
+                "mq attentive pool logits: columns [%d,%d) exceed buffer %d", d->logit_ch_off, d->logit_ch_off + pairs, d->logit_buf);
+  } else if ((rc = check_view(net, d->logit_buf, d->logit_ch_off, pairs * head_ch, "mq attentive pool logits"))) return rc;
+  ASV_REQUIRE(d->out_buf > 0 && d->out_buf < (int)net->bufs.size(), "mq attentive pool: output buffer id %d", d->out_buf);
+  // the two layouts without overlap: [mean | std] per pair, or all means in front of all stds
+  ASV_REQUIRE((d->std_off >= head_ch && d->pair_stride >= d->std_off + head_ch) ||
+              (d->pair_stride >= head_ch && d->std_off >= (pairs - 1) * d->pair_stride + head_ch),
+              "mq attentive pool: pair_stride %d / std_off %d make means and stds of %d-channel heads overlap", d->pair_stride, d->std_off, head_ch);
+  ASV_REQUIRE(d->out_ch_off >= 0 && (long long)d->out_ch_off + (long long)(pairs - 1) * d->pair_stride + d->std_off + head_ch <= net->bufs[d->out_buf].channels,
+              "mq attentive pool: output view exceeds buffer");
+  ASV_REQUIRE(net->is_sequence(net->bufs[d->x_buf].domain) && net->bufs[d->logit_buf].domain == net->bufs[d->x_buf].domain &&
+              net->is_utts(net->bufs[d->out_buf].domain), "mq attentive pool: frames (or a sequence domain) -> utts");
+  Op op; op.kind = OP_MQ_ATTPOOL; op.mq = *d;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
 int asv_net_add_lde_pool(asv_net_t *net, const asv_lde_desc_t *d) {
   ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_lde_pool: net is null or finalized");
   ASV_REQUIRE(d->struct_size == sizeof(asv_lde_desc_t), "asv_net_add_lde_pool: struct_size mismatch");
@@ -880,7 +908,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
         if (k == i || k == i + 1) continue;
         const Op &o = net->ops[k];
         const int reads[] = {o.kind == OP_TDNN ? o.tdnn.in_buf : -1, o.kind == OP_TDNN ? o.tdnn.in2_buf : -1, o.kind == OP_TDNN ? o.tdnn.res_buf : -1,
-                             o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1,
+                             o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.x_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.logit_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
                              o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
@@ -898,7 +926,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
       const Op &o = net->ops[k];
       const int reads[] = {o.kind == OP_TDNN ? o.tdnn.in_buf : -1, o.kind == OP_TDNN ? o.tdnn.in2_buf : -1, o.kind == OP_TDNN ? o.tdnn.res_buf : -1,
                            o.kind == OP_TDNN ? o.tdnn.seg_bias_buf : -1, o.kind == OP_TDNN ? o.tdnn.seg_scale_buf : -1,
-                           o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1,
+                           o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.x_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.logit_buf : -1,
                            o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                            o.kind == OP_ELTWISE ? o.elt.seg_scale_buf : -1, o.kind == OP_ELTWISE ? o.elt.seg_norm_buf : -1, o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
                            o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_IM2COL ? o.i2c.seg_scale_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_GRID_INPUT ? o.gin.in_buf : -1,
@@ -1038,7 +1066,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream) {
 }
 
 unsigned long long asv_kernel_launch_count(int which) {
-  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_TDNN_X3M_IMAGE) ? g_kernel_launches[which].load() : 0ull;
+  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_MQ_ATTPOOL) ? g_kernel_launches[which].load() : 0ull;
 }
 
 size_t asv_net_device_bytes(const asv_net_t *net) {
@@ -1082,6 +1110,10 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
       case OP_ATTPOOL:
         snprintf(line, sizeof(line), "  op %zu: attentive_pool x=%d logits=%d channels=%d -> %d[%d] eps=%g\n", i, op.att.x_buf, op.att.logit_buf, op.att.channels,
                  op.att.out_buf, op.att.out_ch_off, op.att.eps);
+        break;
+      case OP_MQ_ATTPOOL:
+        snprintf(line, sizeof(line), "  op %zu: mq_attentive_pool x=%d logits=%d channels=%d heads=%d queries=%d shared=%d -> %d[%d] eps=%g\n", i, op.mq.x_buf, op.mq.logit_buf,
+                 op.mq.channels, op.mq.heads, op.mq.queries, op.mq.shared_logits, op.mq.out_buf, op.mq.out_ch_off, op.mq.eps);
         break;
       case OP_LDE:
         snprintf(line, sizeof(line), "  op %zu: lde_pool x=%d channels=%d centres=%d -> %d[%d]\n", i, op.lde.x_buf, op.lde.channels, op.lde.n_centres, op.lde.out_buf,
@@ -1699,6 +1731,22 @@ int run_ops(RunCtx &c, size_t n_ops) {
                                    d.channels, dr.seg_row0, dr.seg_len, bp.segments, d.eps,
                                    reinterpret_cast<float *>(net->arena[d.out_buf].ptr) + d.out_ch_off, net->bufs[d.out_buf].ld, net->frames_et(), group, d.logit_softplus2 != 0, op.scale, op.shift, c.s);
         if (rc) return rc;
+        if ((rc = prof.end())) return rc;
+        break;
+      }
+      case OP_MQ_ATTPOOL: {
+        const auto &d = op.mq;
+        const DomainRun &dr = c.dom[net->bufs[d.x_buf].domain];
+        MqPoolKernelParams p;
+        p.x = view(c, d.x_buf, d.x_ch_off); p.ldx = net->bufs[d.x_buf].ld;
+        p.logits = view(c, d.logit_buf, d.logit_ch_off); p.ldl = net->bufs[d.logit_buf].ld;
+        p.channels = d.channels; p.head_ch = d.channels / d.heads;
+        p.seg_row0 = dr.seg_row0; p.seg_len = dr.seg_len; p.eps = d.eps;
+        p.out = reinterpret_cast<float *>(net->arena[d.out_buf].ptr) + d.out_ch_off; p.ld_out = net->bufs[d.out_buf].ld;
+        p.pair_stride = d.pair_stride; p.std_off = d.std_off;
+        if ((rc = prof.begin(K_ATT, 0, (int)i))) return rc;
+        if ((rc = launch_mq_attentive_pool(p, d.queries, d.shared_logits != 0, bp.segments, net->frames_et(), c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_MQ_ATTPOOL];
         if ((rc = prof.end())) return rc;
         break;
       }

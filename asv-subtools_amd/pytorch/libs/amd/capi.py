@@ -21,6 +21,7 @@ POOL_VAR_CLAMP, POOL_VAR_ADD = 0, 1
 PLDA_NORM_NONE, PLDA_NORM_SIMPLE, PLDA_NORM_PSI = 0, 1, 2
 STATUS_HALF_RANGE = 1
 KERNEL_TDNN_P8, KERNEL_TDNN_BIG3, KERNEL_TDNN_P8X, KERNEL_TDNN_CHAINM, KERNEL_TDNN_X3M, KERNEL_TDNN_X3M_IMAGE = 1, 2, 3, 4, 5, 6
+KERNEL_MQ_ATTPOOL = 7
 
 ACT_BY_NAME = {None: ACT_NONE, "": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
@@ -70,6 +71,17 @@ class AttPoolDesc(C.Structure):
         ("shared_logits", C.c_int32),
         ("logit_group", C.c_int32),
         ("logit_softplus2", C.c_int32), ("prior_logit", c_float_p), ("prior_value", c_float_p),
+    ]
+
+
+class MqAttPoolDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("x_buf", C.c_int32), ("x_ch_off", C.c_int32), ("channels", C.c_int32),
+        ("logit_buf", C.c_int32), ("logit_ch_off", C.c_int32),
+        ("heads", C.c_int32), ("queries", C.c_int32), ("shared_logits", C.c_int32),
+        ("out_buf", C.c_int32), ("out_ch_off", C.c_int32), ("pair_stride", C.c_int32), ("std_off", C.c_int32),
+        ("eps", C.c_float),
     ]
 
 
@@ -156,7 +168,7 @@ SYMBOLS = [
     "asv_version", "asv_last_error", "asv_device_count",
     "asv_net_create", "asv_net_destroy", "asv_net_define_grid", "asv_net_new_buffer", "asv_net_add_tdnn",
     "asv_net_add_grid_input", "asv_net_add_im2col", "asv_net_add_grid_flatten",
-    "asv_net_add_stats_pool", "asv_net_add_attentive_pool", "asv_net_add_lde_pool", "asv_net_add_eltwise", "asv_net_add_res2",
+    "asv_net_add_stats_pool", "asv_net_add_attentive_pool", "asv_net_add_mq_attentive_pool", "asv_net_add_lde_pool", "asv_net_add_eltwise", "asv_net_add_res2",
     "asv_net_finalize", "asv_net_embed_dim", "asv_net_describe", "asv_net_extract",
     "asv_net_device_bytes", "asv_net_set_profiling", "asv_net_get_profile", "asv_net_status", "asv_net_status_async", "asv_kernel_launch_count",
     "asv_tdnn_forward", "asv_stats_pool_forward",
@@ -203,6 +215,7 @@ def lib():
     L.asv_net_add_tdnn.argtypes = [vp, C.POINTER(TdnnDesc)]
     L.asv_net_add_stats_pool.argtypes = [vp, C.POINTER(PoolDesc)]
     L.asv_net_add_attentive_pool.argtypes = [vp, C.POINTER(AttPoolDesc)]
+    L.asv_net_add_mq_attentive_pool.argtypes = [vp, C.POINTER(MqAttPoolDesc)]
     L.asv_net_add_lde_pool.argtypes = [vp, C.POINTER(LdeDesc)]
     L.asv_net_add_eltwise.argtypes = [vp, C.POINTER(EltwiseDesc)]
     L.asv_net_add_res2.argtypes = [vp, C.POINTER(Res2Desc)]

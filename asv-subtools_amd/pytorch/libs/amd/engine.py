@@ -77,6 +77,12 @@ def gather_fuse_on():
     return os.environ.get("ASV_AMD_NO_GATHER_FUSE", "0") in ("0", "", "false")
 
 
+def mqpool_on():
+    """ASV_AMD_MQPOOL=0 keeps the heads x queries attentive poolings of a multi-query multi-head pooling (MQMHASP) as separate
+    launches (A/B switch; the one-launch form gives the same bits - tests/test_gpu_mqmha.py)."""
+    return os.environ.get("ASV_AMD_MQPOOL", "1") not in ("0", "false")
+
+
 class Engine(object):
     """One compiled model on one device."""
 
@@ -115,6 +121,8 @@ class Engine(object):
             ops = g.fused_add_ops(ops)               # exact in every precision mode (see its docstring)
             if gather_fuse_on():
                 ops = g.fused_gather_ops(ops)        # likewise: the stage-closing elementwise pass as the prologue of the strided gathers
+            if mqpool_on():
+                ops = g.fused_mqpool_ops(ops)        # likewise: the (head, query) poolings of MQMHASP as one launch
         self.ops = ops                               # the program as uploaded (op indices of the profiling rows refer to it)
         written = sorted({op.out.tid for op in ops} | {op.out2.tid for op in ops if getattr(op, "out2", None) is not None})
         for tid in written:
@@ -186,6 +194,16 @@ class Engine(object):
                     d.prior_logit = op.prior_logit.ctypes.data_as(capi.c_float_p)
                     d.prior_value = op.prior_value.ctypes.data_as(capi.c_float_p)
                 capi.check(L.asv_net_add_attentive_pool(self._net, C.byref(d)), "asv_net_add_attentive_pool")
+            elif op.kind == "mqattpool":
+                d = capi.MqAttPoolDesc()
+                d.struct_size = C.sizeof(capi.MqAttPoolDesc)
+                d.x_buf, d.x_ch_off = bv(op.x)
+                d.channels = op.x.channels
+                d.logit_buf, d.logit_ch_off = bv(op.logits)
+                d.heads, d.queries, d.shared_logits = op.heads, op.queries, int(op.shared)
+                d.out_buf, d.out_ch_off = bv(op.out)
+                d.pair_stride, d.std_off, d.eps = op.pair_stride, op.std_off, op.eps
+                capi.check(L.asv_net_add_mq_attentive_pool(self._net, C.byref(d)), "asv_net_add_mq_attentive_pool")
             elif op.kind == "lde":
                 d = capi.LdeDesc()
                 d.struct_size = C.sizeof(capi.LdeDesc)

@@ -48,7 +48,7 @@ class View(object):
 
 
 class Op(object):
-    """kind in {'tdnn','pool','attpool','eltwise','cat','grid_input','im2col'}; `out` is a View covering
+    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','cat','grid_input','im2col'}; `out` is a View covering
     a whole tensor until concat elision redirects it into a slice of a wider one."""
 
     def __init__(self, kind, out, **attrs):
@@ -60,7 +60,7 @@ class Op(object):
             names = ("inp", "inp2", "seg_bias", "seg_scale", "res")
         elif self.kind == "pool":
             names = ("inp",)
-        elif self.kind == "attpool":
+        elif self.kind in ("attpool", "mqattpool"):
             names = ("x", "logits")
         elif self.kind == "lde":
             names = ("x",)
@@ -76,7 +76,7 @@ class Op(object):
 
     def input_names(self):
         return {"tdnn": ("inp", "inp2", "seg_bias", "seg_scale", "res"), "pool": ("inp",),
-                "attpool": ("x", "logits"), "lde": ("x",), "eltwise": ("a", "b", "c", "seg_scale", "seg_norm", "d"), "cat": (), "grid_input": ("inp",),
+                "attpool": ("x", "logits"), "mqattpool": ("x", "logits"), "lde": ("x",), "eltwise": ("a", "b", "c", "seg_scale", "seg_norm", "d"), "cat": (), "grid_input": ("inp",),
                 "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "flatten": ("inp",)}[self.kind]
 
 
@@ -182,11 +182,13 @@ class Graph(object):
         self.ops.append(Op("flatten", out, inp=inp))
         return out
 
-    def attpool(self, x, logits, eps=1e-5, shared=False, group=0, softplus2=False, prior_logit=None, prior_value=None):
+    def attpool(self, x, logits, eps=1e-5, shared=False, group=0, softplus2=False, prior_logit=None, prior_value=None, mq=None):
         """softmax-over-frames weighted mean / std of x -> [mean | std].  `shared`: logits has ONE channel that weights every
         channel of x; `group` > 1: every `group` consecutive channels of x share logit column (channel // group).
         xi-vector options (per-channel logits): `softplus2` turns the stored values z into logits 2 log(softplus(z));
-        `prior_logit` / `prior_value` [channels] add one more frame with these logits (untransformed) and values."""
+        `prior_logit` / `prior_value` [channels] add one more frame with these logits (untransformed) and values.
+        `mq` = (head, query, heads, queries): the op is one (head, query) pair of a multi-query multi-head pooling (MQMHASP);
+        fused_mqpool_ops() replaces the complete, regularly laid out set of them by one 'mqattpool' op."""
         group = int(group)
         if (softplus2 or prior_logit is not None) and (shared or group > 1):
             raise TraceError("the xi-vector pooling options need per-channel logits")
@@ -196,7 +198,7 @@ class Graph(object):
         out = self.full_view(self.new_tensor(DOMAIN_UTTS, 2 * x.channels))
         f32 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
         self.ops.append(Op("attpool", out, x=x, logits=logits, eps=float(eps), shared=bool(shared), group=group, softplus2=bool(softplus2),
-                           prior_logit=f32(prior_logit), prior_value=f32(prior_value)))
+                           prior_logit=f32(prior_logit), prior_value=f32(prior_value), mq=None if mq is None else tuple(int(v) for v in mq)))
         return out
 
     def lde(self, x, mu, beta):
@@ -436,6 +438,48 @@ class Graph(object):
             out.append(op)
         return out
 
+    def fused_mqpool_ops(self, ops=None, max_queries=4):
+        """The op list with the heads x queries 'attpool' ops of a multi-query multi-head pooling (MQMHASP, pooling.py:590-701 -
+        after cat elision: consecutive ops, pair p = head * queries + query reading head's channel view of ONE tensor and logit
+        columns [p * n, (p + 1) * n) of ONE tensor (n = 1 shared, the head width otherwise), writing [mean | std] to columns
+        [p * 2 width, (p + 1) * 2 width) of ONE pooled tensor) replaced by ONE 'mqattpool' op (kernels_mqpool.hip): every frame of x is
+        read once instead of `queries` times, one launch instead of heads x queries.  The fused kernel forms every (channel, query)
+        sum in the order of the separate launch and writes the same columns, so every bit stays.  Anything that does not match
+        exactly - and more than `max_queries` queries, the kernel's instantiations - is left alone."""
+        ops = list(self.ops if ops is None else ops)
+        out, i = [], 0
+        while i < len(ops):
+            first = ops[i]
+            mq = getattr(first, "mq", None) if first.kind == "attpool" else None
+            fused = None
+            if mq is not None and mq[:2] == (0, 0) and 1 <= mq[3] <= max_queries and mq[2] >= 1 and i + mq[2] * mq[3] <= len(ops):
+                H, Q = mq[2], mq[3]
+                run = ops[i:i + H * Q]
+                Ch = first.x.channels
+                n = 1 if first.shared else Ch
+                ok = (Ch % CHAN_ALIGN == 0 and not first.softplus2 and first.prior_logit is None and first.group <= 1 and first.out.channels == 2 * Ch
+                      and first.x.ch_off + H * Ch <= self.tensors[first.x.tid][1] and not self.is_utts(first.x.tid))
+                for p, o in enumerate(run):
+                    if not ok:
+                        break
+                    h, q = divmod(p, Q)
+                    ok = (o.kind == "attpool" and getattr(o, "mq", None) == (h, q, H, Q) and o.eps == first.eps and o.shared == first.shared
+                          and not o.softplus2 and o.prior_logit is None and o.group <= 1
+                          and o.x == View(first.x.tid, first.x.ch_off + h * Ch, Ch)
+                          and o.logits == View(first.logits.tid, first.logits.ch_off + p * n, n)
+                          and o.out == View(first.out.tid, first.out.ch_off + p * 2 * Ch, 2 * Ch))
+                if ok:
+                    fused = Op("mqattpool", View(first.out.tid, first.out.ch_off, H * Q * 2 * Ch), x=View(first.x.tid, first.x.ch_off, H * Ch),
+                               logits=View(first.logits.tid, first.logits.ch_off, H * Q * n), heads=H, queries=Q, shared=first.shared, eps=first.eps,
+                               pair_stride=2 * Ch, std_off=Ch)
+            if fused is not None:
+                out.append(fused)
+                i += fused.heads * fused.queries
+            else:
+                out.append(first)
+                i += 1
+        return out
+
     def fused_gather_ops(self, ops=None):
         """The op list with every elementwise pass `o = act(a * seg_scale + b)` that only im2col gathers read folded into those
         gathers as their prologue: the output of the last block of a ResNet stage (resnet.py:70-85: relu(se(y) + identity)) feeds
@@ -509,6 +553,8 @@ class Graph(object):
                 ins, extra = repr(op.inp), ""
             elif op.kind == "attpool":
                 ins, extra = "x=%r logits=%r" % (op.x, op.logits), "eps=%g" % op.eps
+            elif op.kind == "mqattpool":
+                ins, extra = "x=%r logits=%r" % (op.x, op.logits), "heads=%d queries=%d shared=%s eps=%g" % (op.heads, op.queries, op.shared, op.eps)
             elif op.kind == "lde":
                 ins, extra = "x=%r" % (op.x,), "centres=%d" % len(op.beta)
             elif op.kind == "eltwise":

@@ -1,8 +1,8 @@
 # -*- coding:utf-8 -*-
 """Pooling layers of the extraction path (reference libs/nnet/pooling.py).  StatisticsPooling (15-76) is on the hot
 path of the target models; AttentiveStatisticsPooling (322-368, single shared head) is the first of the alternative
-poolings of SURVEY.md 8(f) rank 3; the other variants the reference offers are selectable options that this package does
-not implement and says so when constructed."""
+poolings of SURVEY.md 8(f) rank 3; MQMHASP (590-701) is the pooling of the reference's current ECAPA recipe.  What is not
+built (MQMHASP_Linear) says so when constructed."""
 
 import torch
 
@@ -325,4 +325,110 @@ def _not_on_hot_path(name, where):
     return _Unsupported
 
 
-MQMHASP = _not_on_hot_path("MQMHASP", "pooling.py:590-701")
+class MQMHASP(torch.nn.Module):
+    """Multi-query multi-head attentive statistics pooling (reference pooling.py:590-701; Zhao et al., arXiv 2110.05042): the
+    channels are split into `num_head` heads, every head is pooled `num_q` times with its own softmax-over-frames weights -
+    one logit per (head, query, frame) when `share`, one per (head, query, channel, frame) otherwise.  With `time_attention`
+    the attention of head h sees [x_h ; mean_h ; std_h], the utterance's uniform-weight statistics of its own channels.
+    Output [means in (head, query, channel) order | stds in the same order], 2 * num_q * in_dim wide.
+
+    Parameter holder with the reference's sub-module names and shapes (`attention.{0,2,4}`).  On a Sym it records: the
+    global statistics and their hoisted per-utterance bias (the [mean_h ; std_h] columns of the first conv are constant over
+    an utterance), the grouped 1x1 convs as the block-diagonal dense matrices they are, and one attentive pooling per
+    (head, query) on head h's channel view; Graph.fused_mqpool_ops() turns those into ONE kernel launch on the device."""
+
+    def __init__(self, in_dim, num_q=2, num_head=4, hidden_size=128, stddev=True, share=True, affine_layers=2, time_attention=False,
+                 norm_type='batch_norm', **kargs):
+        super(MQMHASP, self).__init__()
+        self.stddev, self.in_dim, self.share, self.hidden_size = stddev, in_dim, share, hidden_size
+        self.num_head, self.num_q, self.time_attention = max(1, num_head), max(1, num_q), time_attention
+        assert (in_dim % num_head) == 0
+        if affine_layers not in (1, 2):
+            raise ValueError("Expected 1 or 2 affine layers, but got {}.".format(affine_layers))
+        if norm_type == 'layer_norm' and affine_layers == 2:
+            raise NotImplementedError("MQMHASP(norm_type='layer_norm'): the GroupNorm between the two attention convs normalises over the "
+                                      "channels of every frame and is not built on the MI355X path; use norm_type='batch_norm'")
+        if norm_type not in ('batch_norm', 'layer_norm'):
+            raise ValueError("Unsupport norm type:{}".format(norm_type))
+        H, Q = self.num_head, self.num_q
+        att_idim = (in_dim * (3 if stddev else 2) if time_attention else in_dim) // H
+        self.att_odim = 1 if share else in_dim // H
+        idim, odim = att_idim * H, self.att_odim * H * Q
+        if affine_layers == 2:
+            self.attention = torch.nn.Sequential(torch.nn.Conv1d(idim, hidden_size * H * Q, kernel_size=1, groups=H), torch.nn.ReLU(),
+                                                 torch.nn.BatchNorm1d(hidden_size * H * Q), torch.nn.Tanh(),
+                                                 torch.nn.Conv1d(hidden_size * H * Q, odim, kernel_size=1, groups=H * Q))
+        else:
+            self.attention = torch.nn.Sequential(torch.nn.Conv1d(idim, odim, kernel_size=1, groups=H))
+        self.out_dim = in_dim * Q * 2 if stddev else in_dim * Q
+
+    @staticmethod
+    def _block_diagonal(conv, in_map):
+        """Dense [out, n_in, 1] weight of a grouped 1x1 conv; `in_map(group)` -> the dense input columns of the group's inputs
+        (-1: the input is left out)."""
+        import numpy as np
+        w = conv.weight.detach().cpu().numpy()
+        go = w.shape[0] // conv.groups
+        cols = [np.asarray(in_map(g)) for g in range(conv.groups)]
+        dense = np.zeros((w.shape[0], int(max(c.max() for c in cols)) + 1, 1), dtype=w.dtype)
+        for g, c in enumerate(cols):
+            dense[g * go:(g + 1) * go, c[c >= 0], 0] = w[g * go:(g + 1) * go, c >= 0, 0]
+        return dense
+
+    def forward(self, x, mask=None):
+        import numpy as np
+        x = _attentive_stats(x, self.in_dim, "MQMHASP")
+        if mask is not None:
+            raise _ir.TraceError("MQMHASP with a frame mask: batches are ragged on the MI355X path, every utterance is pooled over its own frames")
+        g = x.graph
+        C, H, Q, od = self.in_dim, self.num_head, self.num_q, self.att_odim
+        Ch = C // H
+        if Ch % _ir.CHAN_ALIGN != 0:
+            raise _ir.TraceError("MQMHASP: %d channels in %d heads gives heads of %d channels; the head views of the MI355X path need a "
+                                 "multiple of %d" % (C, H, Ch, _ir.CHAN_ALIGN))
+        att = self.attention
+        first = att[0]
+        n_in = first.weight.shape[1]                                       # Ch, or Ch + Ch (+ Ch) with time attention
+        b1 = _ir._np(first.bias)
+        w_x = self._block_diagonal(first, lambda h: np.where(np.arange(n_in) < Ch, h * Ch + np.arange(n_in), -1))
+        w_x = np.ascontiguousarray(w_x[:, :C])
+        seg_bias = None
+        if self.time_attention:
+            # [mean_h ; std_h] are constant over the utterance: W_mean mean + W_std std + b becomes a per-utterance bias
+            gstats = g.pool(x.view, stddev=self.stddev, unbiased=0, var_mode=0, eps=1e-5)
+            nstat = 2 if self.stddev else 1
+            w_ctx = self._block_diagonal(first, lambda h: np.where(np.arange(n_in) >= Ch, ((np.arange(n_in) - Ch) // Ch) * C + h * Ch + np.arange(n_in) % Ch, -1))
+            w_ctx = np.ascontiguousarray(np.pad(w_ctx, ((0, 0), (0, nstat * C - w_ctx.shape[1]), (0, 0))))
+            seg_bias, b1 = g.tdnn(gstats, w_ctx, b1, [0], 0), None
+        if len(att) == 5:
+            bn = att[2]
+            scale, shift = _ir.fold_batchnorm(_ir._np(bn.running_mean), _ir._np(bn.running_var), _ir._np(bn.weight) if bn.affine else None,
+                                              _ir._np(bn.bias) if bn.affine else None, bn.eps)
+            h1 = g.tdnn(x.view, w_x, b1, [0], 0, seg_bias=seg_bias, act1="relu", scale=scale, shift=shift, act2="tanh")
+            hs = self.hidden_size
+            logits = g.tdnn(h1, self._block_diagonal(att[4], lambda k: k * hs + np.arange(hs)), _ir._np(att[4].bias), [0], 0)
+        else:
+            logits = g.tdnn(x.view, w_x, b1, [0], 0, seg_bias=seg_bias)
+        # logit columns: [(h * Q + q) * od, + od) (pooling.py:652: reshape(B, head, q, -1, T))
+        parts = [g.attpool(_ir.View(x.view.tid, x.view.ch_off + h * Ch, Ch), _ir.View(logits.tid, logits.ch_off + (h * Q + q) * od, od),
+                           eps=1e-5, shared=self.share, mq=(h, q, H, Q)) for h in range(H) for q in range(Q)]
+        if H * Q == 1:
+            both = parts[0]
+            return _ir.Sym(g, both if self.stddev else _ir.View(both.tid, both.ch_off, C), 3)
+        # device row: [mean_hq | std_hq] blocks of 2 Ch; reference row: all means in (h, q, c) order, then all stds (pooling.py:655-658)
+        out = g.cat(parts, align=_ir.CHAN_ALIGN)
+        order = np.full(out.channels, -1, dtype=np.int64)
+        for p in range(H * Q):
+            order[p * 2 * Ch:p * 2 * Ch + Ch] = p * Ch + np.arange(Ch)
+            if self.stddev:
+                order[p * 2 * Ch + Ch:(p + 1) * 2 * Ch] = Q * C + p * Ch + np.arange(Ch)
+        return _ir.Sym(g, out, 3, col_order=order)
+
+    def get_output_dim(self):
+        return self.out_dim
+
+    def extra_repr(self):
+        return '(stddev={stddev}, num_head={num_head}, num_q={num_q}, out_dim={out_dim}) '.format(**self.__dict__)
+
+
+MQMHASP_Linear = _not_on_hot_path("MQMHASP_Linear", "pooling.py:704-751")

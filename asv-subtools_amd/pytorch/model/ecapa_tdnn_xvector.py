@@ -7,9 +7,10 @@ sub-module names (hence state_dict keys), `extract_embedding` positions and
 /root/reference/pytorch/model/ecapa_tdnn_xvector.py: Res2NetBlock 17-75, SE_Connect 97-111,
 SE_Res2Block 118-149, AttentiveStatsPool 156-188, ECAPA_TDNN 200-482) - so reference
 `nnet.config` / `*.params` files work unchanged.  Poolings: the default "ecpa-attentive", "attentive"
-(AttentiveStatisticsPooling, reference :275-281) and plain statistics pooling.  "multi-head", "global-multi"
-and "multi-resolution" cannot be constructed in the reference either (its pooling defaults hand
-`time_attention` to AttentionAlphaComponent: TypeError) and "mqmha" is out of scope: they raise.
+(AttentiveStatisticsPooling, reference :275-281), "mqmha" (MQMHASP, reference :289-295 - the pooling of the reference's
+current ECAPA recipe, launcher/runEcapaXvector_roadmap.py:228-238; bn_stats / fc1 / fc2 are then 2 * num_q * mfa_conv wide)
+and plain statistics pooling.  "multi-head", "global-multi" and "multi-resolution" cannot be constructed in the reference
+either (its pooling defaults hand `time_attention` to AttentionAlphaComponent: TypeError): they raise.
 
 All modules are parameter holders whose forward() records fused ops for libasv_amd.so.
 """
@@ -135,14 +136,15 @@ class ECAPA_TDNN(TopVirtualNnet):
         elif pooling in ("multi-head", "global-multi", "multi-resolution"):
             raise TypeError("pooling='%s': the reference's ECAPA_TDNN cannot build this option either - its pooling defaults pass "
                             "`time_attention` on to AttentionAlphaComponent, which does not take it (ecapa_tdnn_xvector.py:213-217, 296-316)" % pooling)
-        elif pooling == "mqmha":
-            raise NotImplementedError("pooling='mqmha' (MQMHASP) is a selectable option of the reference outside the MI355X extraction path "
-                                      "(SURVEY.md section 2, row 3)")
+        elif pooling == "mqmha":                                       # reference :289-295; `stddev` was popped above, so the pooling keeps its own default (True)
+            self.stats = MQMHASP(mfa_dim, **pooling_params)
+            self.bn_stats = nn.BatchNorm1d(self.stats.get_output_dim(), **ecapa_params["bn_params"])
         else:
             self.stats = StatisticsPooling(mfa_dim, stddev=stddev)
             self.bn_stats = nn.BatchNorm1d(mfa_dim * 2)
-        self.fc1 = ReluBatchNormTdnnLayer(mfa_dim * 2, embd_dim, **fc1_params) if fc1 else None
-        self.fc2 = ReluBatchNormTdnnLayer(embd_dim if fc1 else mfa_dim * 2, embd_dim, **fc2_params)
+        stats_dim = self.stats.get_output_dim() if pooling == "mqmha" else mfa_dim * 2
+        self.fc1 = ReluBatchNormTdnnLayer(stats_dim, embd_dim, **fc1_params) if fc1 else None
+        self.fc2 = ReluBatchNormTdnnLayer(embd_dim if fc1 else stats_dim, embd_dim, **fc2_params)
         self.tail_dropout = None
         if training:
             self.loss = MarginSoftmaxLoss_v1(embd_dim, num_targets, **margin_loss_params) if margin_loss else SoftmaxLoss(embd_dim, num_targets)

@@ -178,6 +178,25 @@ typedef struct asv_attpool_desc {
 } asv_attpool_desc_t;
 int asv_net_add_attentive_pool(asv_net_t *net, const asv_attpool_desc_t *d);
 
+/* Multi-query multi-head attentive statistics (libs/nnet/pooling.py:590-701, MQMHASP) as ONE op: the x view holds `heads` heads
+ * of head_ch = channels / heads channels (a multiple of 16); every head is pooled `queries` times (1 .. 4) like
+ * asv_attpool_desc_t does it, pair p = head * queries + query with the softmax over the segment's frames of logit column p
+ * (shared_logits) or of columns [p * head_ch, (p + 1) * head_ch) of the logits view.  Channel j of head h, query q:
+ *   out[p * pair_stride + j] = mean,  out[p * pair_stride + std_off + j] = std = sqrt(max(sum alpha x^2 - mean^2, eps)).
+ * pair_stride = 2 head_ch, std_off = head_ch: [mean | std] blocks per pair, the columns heads * queries separate attentive
+ * poolings write one after the other; pair_stride = head_ch, std_off = heads * queries * head_ch: all means, then all stds -
+ * the reference's row.  Every x row is read once for its `queries` weightings; the sums are formed in the order of the
+ * separate poolings, so the values are theirs to the last bit. */
+typedef struct asv_mq_attpool_desc {
+  uint32_t struct_size;
+  int32_t x_buf, x_ch_off, channels;       /* channels = heads * head_ch */
+  int32_t logit_buf, logit_ch_off;         /* heads * queries * (shared_logits ? 1 : head_ch) columns */
+  int32_t heads, queries, shared_logits;
+  int32_t out_buf, out_ch_off, pair_stride, std_off;
+  float   eps;
+} asv_mq_attpool_desc_t;
+int asv_net_add_mq_attentive_pool(asv_net_t *net, const asv_mq_attpool_desc_t *d);
+
 /* Learnable dictionary encoding pooling (libs/nnet/pooling.py:130-162, LDEPooling): with r = x_t - mu_k,
  * w[t][k] = softmax over the centres k of -beta_k |r|^2, out[c * n_centres + k] = mean over the frames of w[t][k] r[c].
  * mu: host [channels][n_centres]; beta: host [n_centres] (= s^2 + eps); n_centres <= 64; the output view takes
@@ -296,6 +315,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream);
 #define ASV_KERNEL_TDNN_CHAINM 4 /* kernels_tdnn_chainm.hip: the f32x layer chain with its correction products on the scaled 8-bit instruction */
 #define ASV_KERNEL_TDNN_X3M 5    /* kernels_tdnn_x3m.hip: the f32x wide-layer kernel in the same form */
 #define ASV_KERNEL_TDNN_X3M_IMAGE 6 /* launches of that kernel that wrote their output rows as images for an f32m reader (counted in 5 as well) */
+#define ASV_KERNEL_MQ_ATTPOOL 7   /* kernels_pool.hip: mq_attentive_pool_kernel, the one-launch multi-query multi-head attentive pooling */
 unsigned long long asv_kernel_launch_count(int which);
 
 /* Bytes of device memory currently held by the net (weights + activation arena). */
