@@ -462,3 +462,159 @@ def train_plda(vectors, labels, num_iters=10):
                                              offsets.ctypes.data_as(C.POINTER(C.c_longlong)), len(offsets) - 1, int(num_iters),
                                              dp(mean), dp(within), dp(between), _stream(x)), "asv_plda_train")
     return mean, within, between
+
+
+# -------------------------------------------------------------------------------------- PLDA domain adaptation
+
+class PldaCovariances(object):
+    """PLDA model in covariance form: mean [dim], within_var / between_var [dim, dim], float64 - what PldaEstimation keeps
+    (plda_base.py:241-252) and what the domain adaptors of score/pyplda/ivector-adapt-plda-*.py read, change and hand to
+    PLDA.get_output().  `to_plda()` is that last step."""
+
+    def __init__(self, mean, within_var, between_var):
+        self.mean = np.array(mean, dtype=np.float64).reshape(-1)
+        self.dim = self.mean.shape[0]
+        self.within_var = np.array(within_var, dtype=np.float64)
+        self.between_var = np.array(between_var, dtype=np.float64)
+        if self.within_var.shape != (self.dim, self.dim) or self.between_var.shape != (self.dim, self.dim):
+            raise ValueError("PldaCovariances: mean of %d dimensions, within_var %s, between_var %s"
+                             % (self.dim, self.within_var.shape, self.between_var.shape))
+
+    @classmethod
+    def read_stats_ark(cls, path):
+        """The 'mean' / 'within_var' / 'between_var' ark PldaEstimation.plda_write produces (plda_base.py:337-342)."""
+        from libs.support import kaldi_io
+        parts = {k: np.array(v, dtype=np.float64) for k, v in kaldi_io.read_vec_flt_ark(path)}
+        missing = [k for k in ("mean", "within_var", "between_var") if k not in parts]
+        if missing:
+            raise ValueError("%s: no '%s' entry - not a PLDA statistics ark" % (path, "', '".join(missing)))
+        dim = parts["mean"].shape[0]
+        if parts["within_var"].size != dim * dim or parts["between_var"].size != dim * dim:
+            raise ValueError("%s: mean of %d dimensions, covariances of %d / %d values" % (path, dim, parts["within_var"].size, parts["between_var"].size))
+        return cls(parts["mean"], parts["within_var"].reshape(dim, dim), parts["between_var"].reshape(dim, dim))
+
+    def write_stats_ark(self, path):
+        """plda_base.py:337-342: three float64 vectors, the covariances flattened row by row."""
+        from libs.support import kaldi_io
+        with open(path, "wb") as f:
+            kaldi_io.write_vec_flt(f, self.mean, key="mean")
+            kaldi_io.write_vec_flt(f, np.ascontiguousarray(self.within_var).reshape(-1), key="within_var")
+            kaldi_io.write_vec_flt(f, np.ascontiguousarray(self.between_var).reshape(-1), key="between_var")
+
+    def to_plda(self):
+        return Plda.from_covariances(self.mean, self.within_var, self.between_var)
+
+
+def train_plda_covariances(vectors, labels, num_iters=10):
+    """train_plda, returned as the covariance-form model the adaptors below take."""
+    return PldaCovariances(*train_plda(vectors, labels, num_iters=num_iters))
+
+
+def _sym(m):
+    return 0.5 * (m + m.T)
+
+
+def _pd_eigh(m, what):
+    """eigh of a matrix that must be positive definite.  The reference takes sqrt / 1 / sqrt of these eigenvalues unchecked and
+    writes a model full of NaN when one is negative; a zero eigenvalue comes out of LAPACK as +-(a few ulp of the largest), so
+    everything up to dim * eps * largest counts as non-positive (the numerical-rank threshold of numpy.linalg.matrix_rank)."""
+    s, Q = np.linalg.eigh(_sym(m))
+    if not np.isfinite(s).all() or s.min() <= m.shape[0] * np.finfo(np.float64).eps * max(s.max(), 0.0):
+        raise ValueError("%s is not positive definite (smallest eigenvalue %.3g, largest %.3g)" % (what, s.min(), s.max()))
+    # The reference calls sort_svd(s, Q) here (ivector-adapt-plda-coral.py:79-85): a bubble sort that would swap ROWS of Q through
+    # aliasing numpy views.  np.linalg.eigh returns ascending eigenvalues, `s[i] > s[j]` never holds for i < j, the swap never
+    # fires: restated as nothing.
+    return s, Q
+
+
+def _check_same_dim(what, *models):
+    for m in models:
+        if not isinstance(m, PldaCovariances):
+            raise ValueError("%s: a PldaCovariances model is expected, got %s" % (what, type(m).__name__))
+    if len({m.dim for m in models}) != 1:
+        raise ValueError("%s: models of different dimensions (%s)" % (what, ", ".join(str(m.dim) for m in models)))
+
+
+def _coral_step(out_model, adapt_vectors, mean_diff_scale, what):
+    """ivector-adapt-plda-coral.py:40-77.  The statistics add_stats accumulates vector by vector (31-38) come from the device
+    (asv_scatter_f64).  Returns (adaptation mean, A W A^T, A B A^T)."""
+    _check_same_dim(what, out_model)
+    shape = tuple(adapt_vectors.shape) if hasattr(adapt_vectors, "shape") else np.asarray(adapt_vectors).shape
+    if len(shape) != 2 or shape[1] != out_model.dim:
+        raise ValueError("%s: adaptation vectors %s do not fit a %d-dimensional model" % (what, shape, out_model.dim))
+    if shape[0] < 2:
+        raise ValueError("%s: %d adaptation vector(s); a covariance needs at least 2" % (what, shape[0]))
+    total, xtx = second_moments(adapt_vectors)
+    n = float(shape[0])
+    mean = total / n
+    variance = xtx / n - np.outer(mean, mean)
+    mean_diff = mean - out_model.mean
+    variance = variance + mean_diff_scale * np.outer(mean_diff, mean_diff)
+    eigh_o, Q_o = _pd_eigh(out_model.within_var + out_model.between_var, what + ": within_var + between_var of the out-of-domain model")
+    eigh_i, Q_i = _pd_eigh(variance, what + ": the covariance of the %d adaptation vectors (%d dimensions)" % (shape[0], out_model.dim))
+    C_o = (Q_o / np.sqrt(eigh_o)).dot(Q_o.T)                    # Q_o diag(eigh_o)^-1/2 Q_o^T
+    C_i = (Q_i * np.sqrt(eigh_i)).dot(Q_i.T)                    # Q_i diag(eigh_i)^+1/2 Q_i^T
+    A = C_i.dot(C_o)
+    return mean, A.dot(out_model.within_var).dot(A.T), A.dot(out_model.between_var).dot(A.T)
+
+
+def _regularized(base, target, scale, what):
+    """base + scale * B^-T max(0, E - I) B^-1, where B diagonalises both: B^T base B = I, B^T target B = diag(E)
+    (ivector-adapt-plda-coralplus.py:77-85): `base` grows only along the directions in which `target` exceeds it."""
+    s, Q = _pd_eigh(base, what)
+    whiten = (Q / np.sqrt(s)).T                                 # diag(s)^-1/2 Q^T
+    E, P = np.linalg.eigh(_sym(whiten.dot(target).dot(whiten.T)))
+    B_inv = np.linalg.inv(whiten.T.dot(P))
+    return base + scale * B_inv.T.dot(np.diag(np.maximum(0.0, E - 1.0))).dot(B_inv)
+
+
+def coral(out_model, adapt_vectors, mean_diff_scale=1.0):
+    """CORAL (ivector-adapt-plda-coral.py:40-77): A = C_i C_o with C_o = (W + B)^-1/2 of the out-of-domain model and
+    C_i = variance^1/2 of the unlabelled in-domain vectors, so that A (W + B) A^T = variance; W <- A W A^T, B <- A B A^T, the
+    mean becomes the adaptation mean.  Returns a new PldaCovariances."""
+    mean, S_w, S_b = _coral_step(out_model, adapt_vectors, mean_diff_scale, "coral")
+    return PldaCovariances(mean, S_w, S_b)
+
+
+def coral_plus(out_model, adapt_vectors, within_covar_scale=0.8, between_covar_scale=0.8, mean_diff_scale=1.0):
+    """CORAL+ (ivector-adapt-plda-coralplus.py:40-93, defaults of its constructor 19-22): the CORAL step gives pseudo in-domain
+    covariances; the out-of-domain ones grow towards them where those are larger."""
+    mean, S_w, S_b = _coral_step(out_model, adapt_vectors, mean_diff_scale, "coral_plus")
+    return PldaCovariances(mean, _regularized(out_model.within_var, S_w, within_covar_scale, "coral_plus: within_var of the out-of-domain model"),
+                           _regularized(out_model.between_var, S_b, between_covar_scale, "coral_plus: between_var of the out-of-domain model"))
+
+
+def cip(out_model, adapt_vectors, in_model, interpolation_weight=0.5):
+    """CORAL + linear interpolation with a PLDA trained on (little) labelled in-domain data, ivector-adapt-plda-cip.py:104-121;
+    the mean is the in-domain model's (119)."""
+    _check_same_dim("cip", out_model, in_model)
+    _, S_w, S_b = _coral_step(out_model, adapt_vectors, 1.0, "cip")
+    a = interpolation_weight
+    return PldaCovariances(in_model.mean, a * S_w + (1 - a) * in_model.within_var, a * S_b + (1 - a) * in_model.between_var)
+
+
+def cip_reg(out_model, adapt_vectors, in_model, interpolation_weight=0.5):
+    """CORAL + regularised interpolation, ivector-adapt-plda-cip-reg.py:107-128: the in-domain covariances grow towards the
+    CORAL-adapted ones; the mean stays the in-domain model's (main(), 169-174)."""
+    _check_same_dim("cip_reg", out_model, in_model)
+    _, S_w, S_b = _coral_step(out_model, adapt_vectors, 1.0, "cip_reg")
+    return PldaCovariances(in_model.mean, _regularized(in_model.within_var, S_w, interpolation_weight, "cip_reg: within_var of the in-domain model"),
+                           _regularized(in_model.between_var, S_b, interpolation_weight, "cip_reg: between_var of the in-domain model"))
+
+
+def lip(out_model, in_model, interpolation_weight=0.4):
+    """Linear interpolation of two PLDA models, ivector-adapt-plda-lip.py:26-34: weight * out-of-domain + (1 - weight) *
+    in-domain, in-domain mean."""
+    _check_same_dim("lip", out_model, in_model)
+    a = interpolation_weight
+    return PldaCovariances(in_model.mean, a * out_model.within_var + (1 - a) * in_model.within_var,
+                           a * out_model.between_var + (1 - a) * in_model.between_var)
+
+
+def lip_reg(out_model, in_model, interpolation_weight=0.6):
+    """Regularised interpolation, ivector-adapt-plda-lip-reg.py:26-48: the in-domain covariances grow towards the out-of-domain
+    ones by (1 - weight) of the excess (40, 48); in-domain mean (49)."""
+    _check_same_dim("lip_reg", out_model, in_model)
+    a = 1 - interpolation_weight
+    return PldaCovariances(in_model.mean, _regularized(in_model.within_var, out_model.within_var, a, "lip_reg: within_var of the in-domain model"),
+                           _regularized(in_model.between_var, out_model.between_var, a, "lip_reg: between_var of the in-domain model"))

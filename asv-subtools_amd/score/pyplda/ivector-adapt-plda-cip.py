@@ -1,0 +1,32 @@
+# -*- coding:utf-8 -*-
+"""CIP (CORAL + linear interpolation) domain adaptation of a PLDA model on an MI355X - command-line compatible with the
+reference's score/pyplda/ivector-adapt-plda-cip.py: out-of-domain PLDA statistics ark + unlabelled in-domain vectors +
+in-domain PLDA statistics ark -> Kaldi text <Plda> (libs.amd.scoring.cip, weight 0.5).
+
+    python3 ivector-adapt-plda-cip.py [--gpu-id N] <plda-out-domain> <adapt-ivector-rspecifier> <plda-in-domain> <plda-adapt>
+"""
+
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import adapt_common as common  # noqa: E402
+
+USAGE = "<plda-out-domain> <adapt-ivector-rspecifier> <plda-in-domain> <plda-adapt>"
+
+
+def main():
+    args, gpu_id = common.parse(sys.argv, USAGE, 4)
+
+    def body():
+        from libs.amd import scoring
+        common.select_device(gpu_id)
+        out_model = scoring.PldaCovariances.read_stats_ark(args[0])
+        in_model = scoring.PldaCovariances.read_stats_ark(args[2])
+        scoring.cip(out_model, common.read_vectors(args[1]), in_model).to_plda().write_kaldi_text(args[3])
+    common.run(body)
+
+
+if __name__ == "__main__":
+    main()
