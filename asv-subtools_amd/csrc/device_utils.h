@@ -168,6 +168,35 @@ __device__ __forceinline__ X3Frag x3_split(const uint4 a, const uint4 b, uint32_
   return f;
 }
 
+// ---- the operand split of the "f32m" form of the f32x mode (kernels_tdnn_chainm.hip - the arithmetic is explained there - and
+// kernels_tdnn_x3m.hip, which writes the images chainm reads: both MUST split alike)
+// E8M0 block scales (2^(byte - 127)) that undo the host's / the epilogue's scaling of the 8-bit operands:
+//   w_hi8 = e4m3(w_hi 2^-6), w_lo8 = e4m3(w_lo 2^6)   (pack_tdnn_weight_mx8: w_hi < 2^14, |w_lo| <= 2^-11 |w_hi|)
+//   x_lo8 = e5m2(x_lo 2^11), x_hi8 = e5m2(x)
+constexpr int kScaleWhi = 127 + 6, kScaleWlo = 127 - 6, kScaleXlo = 127 - 11, kScaleXhi = 127;
+typedef int v8i __attribute__((ext_vector_type(8)));         // an operand of the scaled 8-bit matrix instruction
+
+// Range watch of this form: a packed pair of hi halves -> bits 15 / 31 set iff |half| >= 57344 (0x7b00 + 0x0500 carries into bit 15),
+// inf and NaN included: beyond it e5m2(x) has no finite value.  Published as ASV_STATUS_HALF_RANGE like the half split's own watch;
+// the callers re-run such a batch on the bf16-halves twin.
+__device__ __forceinline__ uint32_t mx_range_bits(uint32_t packed_hi) { return (packed_hi & 0x7fff7fffu) + 0x05000500u; }
+
+// two f32 -> the packed pair of hi halves, and the two 8-bit pairs (low 16 bits of hi8 / lo8 when SEL = false, high 16 bits otherwise)
+template <bool SEL>
+__device__ __forceinline__ void split_mx(float v0, float v1, uint32_t &hi16, int &hi8, int &lo8, uint32_t &range) {
+  hi16 = pack_h16x2<ET_F16>(v0, v1);
+  range |= mx_range_bits(hi16);
+  float r0, r1;
+  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi16), "v"(v0));
+  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi16), "v"(v1));
+  hi8 = __builtin_amdgcn_cvt_pk_bf8_f32(v0, v1, hi8, SEL);
+  lo8 = __builtin_amdgcn_cvt_pk_bf8_f32(r0 * 2048.0f, r1 * 2048.0f, lo8, SEL);
+}
+
+// tag arguments of the chain kernels' generic lambdas: TrYes = the matrix instruction with swapped operands (lane = channel)
+struct TrNo { static constexpr bool value = false; };
+struct TrYes { static constexpr bool value = true; };
+
 // max(v, lo) as ONE instruction.  fmaxf() costs three on this target: IEEE mode makes the compiler quiet both operands
 // (v_max_f32 x, x, x) in front of the real v_max_f32 (and it folds __builtin_amdgcn_fmed3f(v, lo, inf) back into the same) - 256
 // extra VALU operations in a 128-register epilogue, next to a partner wave whose MFMA stream leaves a VALU operation ~14 cycles.

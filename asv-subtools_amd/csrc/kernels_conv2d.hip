@@ -18,7 +18,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -35,23 +35,8 @@ __device__ __forceinline__ int conv_abl(const TdnnKernelParams &p) { return p.tu
 __device__ __forceinline__ constexpr int conv_abl(const TdnnKernelParams &) { return 0; }
 #endif
 
-typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-
 template <int CIN> __device__ __forceinline__ int cswz(int row, int slot) {
-  return CIN == 32 ? (slot ^ ((row >> 2) & 3)) : (slot ^ ((row >> 1) & 7));
-}
-
-__device__ __forceinline__ void conv_glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
+  return CIN == 32 ? (slot ^ ((row >> 2) & 3)) : lds_swz(row, slot);
 }
 
 // weights: [tap][k-group][n-fragment][lane = (k half lh, channel lr)][8] bf16, k = kg * 16 + lh * 8 + e
@@ -70,12 +55,12 @@ __global__ __launch_bounds__(256, CIN == 32 ? 3 : 2) void grid_conv_narrow_kerne
 
   // ---- window: one LDS-DMA instruction per 1 KiB piece, rows clamped onto the matrix (its first / last rows are gaps)
   const unsigned char *xg = reinterpret_cast<const unsigned char *>(p.x);
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte_t *)win);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)win);
   for (int piece = wave; piece < PIECES; piece += 4) {
     const int w = piece * RPP + lane / SLOTS;
     const int row = min(max(m0 - CHALO + w, 0), p.rows - 1);
     const int src_slot = cswz<CIN>(w, lane % SLOTS);
-    conv_glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + piece * 1024));
+    glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + piece * 1024));
   }
   const int v_taps = p.taps[lane < 9 ? lane : 0];
   const uint4 *wf = reinterpret_cast<const uint4 *>(p.wconv) + lane;            // fragment f at wf[f * 64]
@@ -232,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void grid_conv_narrow_pers_kernel(const Tdn
   if (t_begin >= t_end) return;
 
   const unsigned char *xg = reinterpret_cast<const unsigned char *>(p.x);
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte_t *)ring);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)ring);
   // `count` 1 KiB pieces of window rows starting at virtual row v0 (virtual row v = matrix row v - HALO, clamped onto the matrix:
   // its first / last rows are gaps); a piece's ring position is its virtual row modulo the ring
   auto fetch = [&](int v0, int count) {
@@ -242,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void grid_conv_narrow_pers_kernel(const Tdn
       const int rrow = rbase + lane / G::SLOTS;                  // ring row of this lane's 16 bytes
       const int row = min(max(v - G::HALO + lane / G::SLOTS, 0), p.rows - 1);
       const int src_slot = cswz<CIN>(rrow, lane % G::SLOTS);
-      conv_glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)rbase * G::ROWB));
+      glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)rbase * G::ROWB));
     }
   };
   fetch(t_begin * G::BM, (G::WIN + (min(t_end - t_begin, G::PF) - 1) * G::BM) / G::RPP);          // the first window + the rows of the next PF - 1 tiles
@@ -379,13 +364,13 @@ __global__ __launch_bounds__(256, 2) void grid_conv_wide_kernel(const TdnnKernel
 
   // ---- window: one LDS-DMA instruction per 1 KiB piece, rows clamped onto the matrix (its first / last rows are gaps)
   const unsigned char *xg = reinterpret_cast<const unsigned char *>(p.x);
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte_t *)win);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)win);
   for (int piece = wave; piece < G::PIECES; piece += 4) {
     if (conv_abl(p) & 4) break;                                            // developer aid (ASV_AMD_CONV_ABL bit 2): no window fetch
     const int w = piece * G::RPP + lane / G::SLOTS;
     const int row = min(max(m0 - G::HALO + w, 0), p.rows - 1);
     const int src_slot = (lane % G::SLOTS) ^ (w & 15);
-    conv_glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + piece * 1024));
+    glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + piece * 1024));
   }
   const int v_taps = p.taps[lane < 9 ? lane : 0];
   // The epilogue's per-channel constants, fetched NOW, one to three floats per thread (bias | scale | shift, CIN each): behind the K
@@ -534,12 +519,12 @@ __global__ __launch_bounds__(256, 2) void grid_conv_s2d_kernel(const TdnnKernelP
   const int m0 = xcd_swizzle(blockIdx.x, gridDim.x) * S2D_BM;
 
   const unsigned char *xg = reinterpret_cast<const unsigned char *>(p.x);
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte_t *)win);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)win);
   for (int piece = wave; piece < PIECES; piece += 4) {
     const int w = piece * RPP + lane / SLOTS;
     const int row = min(max(m0 - S2D_HLO + w, 0), p.rows - 1);
     const int src_slot = (lane % SLOTS) ^ (w & 15);
-    conv_glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + piece * 1024));
+    glds16(xg + (size_t)row * ((size_t)p.ldx * 2) + src_slot * 16, __builtin_amdgcn_readfirstlane(lds_base + piece * 1024));
   }
   const int v_taps = p.taps[lane < S2D_NT ? lane : 0];
   // bias | scale | shift of the 64 output channels: fetched now by the first 192 threads, handed out through LDS behind the K loop

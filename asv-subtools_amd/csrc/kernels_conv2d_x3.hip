@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 #include "host_convert.h"
 
 namespace asv {
@@ -32,8 +32,6 @@ namespace {
 
 constexpr int QROWB = 128;          // image row: 32 channels as [hi 64 B | lo 64 B]
 constexpr int QCH = 32;             // channels per chunk
-
-__device__ __forceinline__ int qswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
 
 template <int WM_, int WN_, int MF_, int NFW_, int HLO_, int HHI_, int NBUF_>
 struct QGeom {
@@ -126,8 +124,8 @@ __global__ __launch_bounds__(256, 2) void grid_conv_x3_kernel(const TdnnKernelPa
         const bool ok = (st.ok >> it) & 1u;
         const uint4 zero = make_uint4(0, 0, 0, 0);
         const X3Frag f = x3_split<ET, true>(ok ? st.a[it] : zero, ok ? st.b[it] : zero, range);
-        *reinterpret_cast<uint4 *>(img + w * QROWB + qswz(w, q) * 16) = f.hi;
-        *reinterpret_cast<uint4 *>(img + w * QROWB + qswz(w, 4 + q) * 16) = f.lo;
+        *reinterpret_cast<uint4 *>(img + w * QROWB + lds_swz(w, q) * 16) = f.hi;
+        *reinterpret_cast<uint4 *>(img + w * QROWB + lds_swz(w, 4 + q) * 16) = f.lo;
       }
     }
   };
@@ -150,8 +148,8 @@ __global__ __launch_bounds__(256, 2) void grid_conv_x3_kernel(const TdnnKernelPa
 #pragma unroll
     for (int k = 0; k < UI; ++k) {
       const int w = wrow0 + (u * UI + k) * 32 + d;
-      x.h[k] = *reinterpret_cast<const uint4 *>(img + w * QROWB + qswz(w, kg * 2 + lh) * 16);
-      x.l[k] = *reinterpret_cast<const uint4 *>(img + w * QROWB + qswz(w, 4 + kg * 2 + lh) * 16);
+      x.h[k] = *reinterpret_cast<const uint4 *>(img + w * QROWB + lds_swz(w, kg * 2 + lh) * 16);
+      x.l[k] = *reinterpret_cast<const uint4 *>(img + w * QROWB + lds_swz(w, 4 + kg * 2 + lh) * 16);
     }
   };
 
@@ -405,8 +403,8 @@ __global__ __launch_bounds__(256, 2) void grid_conv_x3_pers32_kernel(const TdnnK
       const bool ok = (st.ok >> it) & 1u;
       const uint4 zero = make_uint4(0, 0, 0, 0);
       const X3Frag f = x3_split<ET, true>(ok ? st.a[it] : zero, ok ? st.b[it] : zero, range);
-      *reinterpret_cast<uint4 *>(lds + rr * QROWB + qswz(rr, q) * 16) = f.hi;
-      *reinterpret_cast<uint4 *>(lds + rr * QROWB + qswz(rr, 4 + q) * 16) = f.lo;
+      *reinterpret_cast<uint4 *>(lds + rr * QROWB + lds_swz(rr, q) * 16) = f.hi;
+      *reinterpret_cast<uint4 *>(lds + rr * QROWB + lds_swz(rr, 4 + q) * 16) = f.lo;
     }
   };
 
@@ -467,8 +465,8 @@ __global__ __launch_bounds__(256, 2) void grid_conv_x3_pers32_kernel(const TdnnK
       int rr = wb + lr + d;
       rr = rr < 0 ? rr + G::RING : (rr >= G::RING ? rr - G::RING : rr);
       const unsigned char *rowp = lds + rr * QROWB;
-      h = *reinterpret_cast<const uint4 *>(rowp + qswz(rr, kg * 2 + lh) * 16);
-      l = *reinterpret_cast<const uint4 *>(rowp + qswz(rr, 4 + kg * 2 + lh) * 16);
+      h = *reinterpret_cast<const uint4 *>(rowp + lds_swz(rr, kg * 2 + lh) * 16);
+      l = *reinterpret_cast<const uint4 *>(rowp + lds_swz(rr, 4 + kg * 2 + lh) * 16);
     };
     read_x(0, 0, xh[0], xl[0]);
 #pragma unroll

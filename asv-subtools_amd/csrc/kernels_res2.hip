@@ -37,7 +37,7 @@
 // iteration i - 1), so no other wave's read can meet the DMA.
 #include <algorithm>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -61,21 +61,6 @@ struct Res2Geom {
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 static_assert(7 * kHalo <= RMARGIN && kHalo <= RPAD, "margin must cover seven branches of the largest dilation");
 
-typedef __attribute__((address_space(3))) unsigned char res2_lds_byte;
-
-__device__ __forceinline__ void res2_glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
 template <int ET, int FR>
 __global__ __launch_bounds__(512, 2) void res2_chain_kernel(const Res2KernelParams p) {
   using G = Res2Geom<FR>;
@@ -89,7 +74,7 @@ __global__ __launch_bounds__(512, 2) void res2_chain_kernel(const Res2KernelPara
   const int rbase = rh * NA * 32;                         // first window row of this wave
   const bool full = (FR % 2 == 0) || rh == 0;             // this wave has NA fragments (otherwise NA - 1): wave-uniform
   const int d = p.dilation;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(res2_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   const unsigned char *hg = reinterpret_cast<const unsigned char *>(p.x);
   unsigned char *og = reinterpret_cast<unsigned char *>(p.y);
   const size_t x_pitch = (size_t)p.ldx * 2, y_pitch = (size_t)p.ldy * 2;
@@ -108,7 +93,7 @@ __global__ __launch_bounds__(512, 2) void res2_chain_kernel(const Res2KernelPara
       const int grow = min(max(m0 - RMARGIN + r, 0), p.rows - 1);   // beyond the ends: the first / last row are zero gap rows
       const int slot = (lane_e & 15) ^ ((row0 + r) & 15);
       const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + off + (uint32_t)(row0 * RROWB) + (uint32_t)piece * 1024u);
-      res2_glds16(hg + (size_t)grow * x_pitch + (size_t)g * RROWB + (size_t)slot * 16, dst);
+      glds16(hg + (size_t)grow * x_pitch + (size_t)g * RROWB + (size_t)slot * 16, dst);
     }
   };
 

@@ -26,7 +26,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -46,8 +46,6 @@ template <int HALO> struct Geom {
   static constexpr int NA = (A_PIECES + 255) / 256;      // 16-byte window pieces per thread
 };
 static_assert(kRowTile % BM == 0, "row padding must be a multiple of the M tile");
-
-__device__ __forceinline__ int swz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
 
 template <int ET, bool OUT16, bool GENERIC, int HALO>
 __global__ __launch_bounds__(256, HALO <= 24 ? 2 : 1) void tdnn_gemm_kernel(const TdnnKernelParams p, int m_tiles, int n_tiles) {
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(256, HALO <= 24 ? 2 : 1) void tdnn_gemm_kernel(cons
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int q = i * 256 + tid, n = q >> 3, slot = q & 7;
-      *reinterpret_cast<uint4 *>(Bb + n * ROWB + swz(n, slot) * 16) = regB[i];
+      *reinterpret_cast<uint4 *>(Bb + n * ROWB + lds_swz(n, slot) * 16) = regB[i];
     }
   };
   auto sstore_A = [&](int stage) {
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(256, HALO <= 24 ? 2 : 1) void tdnn_gemm_kernel(cons
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       const int q = i * 256 + tid, w = q >> 3, slot = q & 7;
-      if (q < A_PIECES) *reinterpret_cast<uint4 *>(Ab + w * ROWB + swz(w, slot) * 16) = regA[i];
+      if (q < A_PIECES) *reinterpret_cast<uint4 *>(Ab + w * ROWB + lds_swz(w, slot) * 16) = regA[i];
     }
   };
   auto mma_group = [&](const unsigned char *Ab, const unsigned char *Bb, int d, int kg) {
@@ -136,12 +134,12 @@ __global__ __launch_bounds__(256, HALO <= 24 ? 2 : 1) void tdnn_gemm_kernel(cons
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int w = wm * 64 + i * 32 + lr + HALO + d;
-      a[i] = *reinterpret_cast<const uint4 *>(Ab + w * ROWB + swz(w, slot) * 16);
+      a[i] = *reinterpret_cast<const uint4 *>(Ab + w * ROWB + lds_swz(w, slot) * 16);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int n = wn * 64 + j * 32 + lr;
-      b[j] = *reinterpret_cast<const uint4 *>(Bb + n * ROWB + swz(n, slot) * 16);
+      b[j] = *reinterpret_cast<const uint4 *>(Bb + n * ROWB + lds_swz(n, slot) * 16);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)

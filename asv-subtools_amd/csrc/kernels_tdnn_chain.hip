@@ -51,7 +51,8 @@
 // One workgroup (512 threads, 160 KiB LDS) per CU.
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "chain_pool.h"
+#include "lds_dma.h"
 
 #ifndef CHAIN_EXP
 #define CHAIN_EXP 0      // experiment builds: bit 0 / 1 = the Y loops fetch only one / none of the two weight fragments per k-group, bit 2 = every chunk fetches the SAME fragments (results garbage)
@@ -80,25 +81,7 @@ template <int MF> struct ChainGeom {
   static_assert(LDS <= 163840, "160 KiB of LDS per CU");
 };
 
-typedef __attribute__((address_space(3))) unsigned char chain_lds_byte;
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
-struct TrNo { static constexpr bool value = false; };
-struct TrYes { static constexpr bool value = true; };
-
-__device__ __forceinline__ int cswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void chain_glds16_s(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 
 // POOLV: pooling epilogue of the last layer.  0 = first version (per-lane segment tracking, register-by-register seams);
 //        1 = run-based (default): every utterance inside a 32-frame fragment is one masked run over all 16 registers,
@@ -118,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // 0..7: channel slice of phases 1-2, unit index of the last
   const int lr = lane & 31, lh = lane >> 5;
   const int m0 = p.row_base + blockIdx.x * CM;                      // (row_base / tile_base: the launch's first row and tile, launch_tdnn_chain)
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(chain_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   float *par = reinterpret_cast<float *>(lds + SCR_OFF);            // bias[512] | scale[512] | shift[512] of the layer in flight
 
   // developer aid: [workgroup][wave][32] s_memtime stamps; 0..12 phase boundaries, 14 / 15 s_memrealtime at start / end,
@@ -173,7 +156,6 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
     }
   };
 
-
   // ================================ phase 1: layer A through the window ring ================================
   stage_params(p.first);
   {
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
       const int grp = min(wave + i * 8, CGROUPS - 1);
       const int w = grp * 8 + g_row;
       const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-      a_off[i] = (uint32_t)row * (uint32_t)x_pitch + (uint32_t)cswz(w, g_slot) * 16u;
+      a_off[i] = (uint32_t)row * (uint32_t)x_pitch + (uint32_t)lds_swz(w, g_slot) * 16u;
     }
     auto issue_A = [&](int c, int st) {
       const unsigned char *base = xg + (size_t)c * (CBK * 2);
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
       for (int i = 0; i < CPIECES; ++i) {
         const int grp = min(wave + i * 8, CGROUPS - 1);
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + st * CSTAGE + grp * 1024);
-        chain_glds16_s(base, a_off[i], dst);
+        glds16_s(base, a_off[i], dst);
       }
     };
     // Instruction diet (the SIMD's issue slots are what two co-resident waves really share - a wave in an epilogue gets
@@ -404,10 +386,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
     const TdnnChainLayer &L = p.last;
     const float act_lo = L.relu ? 0.0f : -INFINITY;
     const int half = p.tile_base + (int)blockIdx.x;      // index of this tile's partial-moment block
-    int first_seg = -1;
-#pragma unroll
-    for (int k = 0; k < kHalo + 1; ++k)
-      if (first_seg < 0 && m0 + k < p.rows) first_seg = p.row_seg[m0 + k];
+    const int first_seg = pool_first_seg(p, m0);
     // row -> utterance of the tile's rows (-1: gap row; rows beyond the tile - the 96-frame form - or beyond the matrix count as gaps)
     const int rowseg_lo = (m0 + lane < p.rows) ? p.row_seg[m0 + lane] : -1;
     const int rowseg_hi = (64 + lane < CM && m0 + 64 + lane < p.rows) ? p.row_seg[m0 + 64 + lane] : -1;
@@ -438,17 +417,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
         float ps[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f}, pv[2] = {0.f, 0.f};
         int cur_seg = -1;                    // per lane: the halves cross an utterance seam at different registers
         auto publish = [&](bool mine) {      // lanes with `mine` write the moments of their current segment
-          const int slot = cur_seg - first_seg;
-          if (mine && cur_seg >= 0 && slot >= 0 && slot < p.pool_slots) {
-            float *dst = p.pool_partial + ((size_t)((half * p.pool_slots + slot) * 2 + lh) * 3) * p.ld_partial + cb + lr;
-  #pragma unroll
-            for (int j = 0; j < 2; ++j)
-              if (cb + j * 32 + lr < p.ld_partial) {
-                dst[j * 32] = ps[j] * sc[j];
-                dst[j * 32 + p.ld_partial] = pq[j] * sc[j] * sc[j];
-                dst[j * 32 + 2 * p.ld_partial] = pv[j] * sc[j];
-              }
-          }
+          if (mine) pool_publish_moments(p, half, first_seg, cur_seg, cb, lr, lh, ps, pq, pv, sc);
         };
   #pragma unroll
         for (int i = 0; i < MF; ++i) {
@@ -517,18 +486,8 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
         int cur_seg = -1;                    // uniform: all lanes walk the utterances of the tile together
         bool have = false;                   // per lane: pv is a frame of cur_seg (the lane has had a frame of it in this tile)
         auto publish = [&]() {
-          const int slot = cur_seg - first_seg;
           if constexpr (ABL == 2) { asm volatile("" ::"v"(ps[0]), "v"(ps[1]), "v"(pq[0]), "v"(pq[1]), "v"(pv[0]), "v"(pv[1])); return; }
-          if (cur_seg >= 0 && slot >= 0 && slot < p.pool_slots) {
-            float *dst = p.pool_partial + ((size_t)((half * p.pool_slots + slot) * 2 + lh) * 3) * p.ld_partial + cb + lr;
-  #pragma unroll
-            for (int j = 0; j < 2; ++j)
-              if (cb + j * 32 + lr < p.ld_partial) {
-                dst[j * 32] = ps[j] * sc[j];
-                dst[j * 32 + p.ld_partial] = pq[j] * sc[j] * sc[j];
-                dst[j * 32 + 2 * p.ld_partial] = pv[j] * sc[j];
-              }
-          }
+          pool_publish_moments(p, half, first_seg, cur_seg, cb, lr, lh, ps, pq, pv, sc);
         };
   #pragma unroll
         for (int i = 0; i < MF; ++i) {
@@ -580,11 +539,8 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
               // a seam or gap rows: register r of this lane holds frame 8 (r >> 2) + 4 lh + (r & 3) -> bit r of the lane's mask
               const uint32_t x = bits >> (4 * lh);
               const uint32_t lm = (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
-              // pivot = the lane's FIRST frame of the utterance, in whichever fragment of the tile that frame lies.  (Until round 5
-              // it was only taken in the utterance's first fragment: a lane half without a frame there - an utterance that starts in
-              // the last rows of a fragment - kept the PREVIOUS utterance's pivot for the rest of the tile.  Harmless between
-              // utterances of like scale; next to one whose activations are 1e5 x larger the sums about that pivot cancelled and the
-              // embedding depended on its batch neighbour: tests/test_gpu_xvector.py::test_pooled_moments_ignore_the_neighbour.)
+              // pivot = the lane's FIRST frame of the utterance, in whichever fragment of the tile that frame lies (the pivot rule:
+              // chain_pool.h chain64_pool_epilogue, the 64-frame chains' form of this walk)
               const bool need = !have && lm != 0;
               if (__builtin_amdgcn_ballot_w64(need) != 0) {
                 const int rsel = need ? __builtin_ctz(lm) : 16;

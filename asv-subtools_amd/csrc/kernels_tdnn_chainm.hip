@@ -45,7 +45,8 @@
 // Alternating the issue priority between the two waves of a SIMD step by step gives 3 % (r6p).
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "chain_pool.h"
+#include "lds_dma.h"
 
 #ifndef CHAINM_EXP
 #define CHAINM_EXP 0
@@ -70,48 +71,6 @@ constexpr int MRING = 10;                  // image rows in (p.x_image): window 
 static_assert(MRING * MSTG <= 2 * MYIMG, "layer A's window buffers live inside the Y region (Yh + Y8)");
 static_assert(CHAINM_LDS <= 163840, "160 KiB of LDS per CU");
 
-// E8M0 block scales (2^(byte - 127)) that undo the host's / the epilogue's scaling of the 8-bit operands:
-//   w_hi8 = e4m3(w_hi 2^-6), w_lo8 = e4m3(w_lo 2^6)   (pack_tdnn_weight_mx8: w_hi < 2^14, |w_lo| <= 2^-11 |w_hi|)
-//   x_lo8 = e5m2(x_lo 2^11), x_hi8 = e5m2(x)
-constexpr int kScaleWhi = 127 + 6, kScaleWlo = 127 - 6, kScaleXlo = 127 - 11, kScaleXhi = 127;
-
-typedef __attribute__((address_space(3))) unsigned char chainm_lds_byte;
-typedef int mx_v8i __attribute__((ext_vector_type(8)));
-struct MTrNo { static constexpr bool value = false; };
-struct MTrYes { static constexpr bool value = true; };
-
-__device__ __forceinline__ int mswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void chainm_glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-// Range watch of this form: a packed pair of hi halves -> bits 15 / 31 set iff |half| >= 57344 (0x7b00 + 0x0500 carries into bit 15),
-// inf and NaN included: beyond it e5m2(x) has no finite value.  Published as ASV_STATUS_HALF_RANGE like the half split's own watch;
-// the callers re-run such a batch on the bf16-halves twin.
-__device__ __forceinline__ uint32_t mx_range_bits(uint32_t packed_hi) { return (packed_hi & 0x7fff7fffu) + 0x05000500u; }
-
-// two f32 -> the packed pair of hi halves, and the two 8-bit pairs (low 16 bits of hi8 / lo8 when SEL = false, high 16 bits otherwise)
-template <bool SEL>
-__device__ __forceinline__ void split_mx(float v0, float v1, uint32_t &hi16, int &hi8, int &lo8, uint32_t &range) {
-  hi16 = pack_h16x2<ET_F16>(v0, v1);
-  range |= mx_range_bits(hi16);
-  float r0, r1;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi16), "v"(v0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi16), "v"(v1));
-  hi8 = __builtin_amdgcn_cvt_pk_bf8_f32(v0, v1, hi8, SEL);
-  lo8 = __builtin_amdgcn_cvt_pk_bf8_f32(r0 * 2048.0f, r1 * 2048.0f, lo8, SEL);
-}
-
 // IMG: the first layer's input rows are images (p.x_image).  DEV: the instantiation with the developer aids compiled in (per-step stamps,
 // ASV_AMD_CHAINM_ABL, the x_image == 2 protocol); the production instantiations carry none of their tests in the K loops (layer A's loop
 // was 269 scalar + 143 vector instructions per 24 matrix instructions with all of them in, round 6).
@@ -123,7 +82,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
   const int lr = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * MM;
   uint32_t range = 0u;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(chainm_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   float *par = reinterpret_cast<float *>(lds + MPAR);
   const uint32_t lane16 = (uint32_t)lane * 16u;
   const int scale_w = lh ? kScaleWlo : kScaleWhi, scale_x = lh ? kScaleXhi : kScaleXlo;
@@ -209,11 +168,11 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
   auto mma_mx = [&](const MW &w, const MX8 &e, int q, auto tr) {
     const int i = q & 1, j = q >> 1;
 #if CHAINM_WHI8_REG
-    const mx_v8i a = {(int)wq[j].x, (int)wq[j].y, (int)wq[j].z, (int)wq[j].w, (int)w.e[j].x, (int)w.e[j].y, (int)w.e[j].z, (int)w.e[j].w};
+    const v8i a = {(int)wq[j].x, (int)wq[j].y, (int)wq[j].z, (int)wq[j].w, (int)w.e[j].x, (int)w.e[j].y, (int)w.e[j].z, (int)w.e[j].w};
 #else
-    const mx_v8i a = {(int)w.q[j].x, (int)w.q[j].y, (int)w.q[j].z, (int)w.q[j].w, (int)w.e[j].x, (int)w.e[j].y, (int)w.e[j].z, (int)w.e[j].w};
+    const v8i a = {(int)w.q[j].x, (int)w.q[j].y, (int)w.q[j].z, (int)w.q[j].w, (int)w.e[j].x, (int)w.e[j].y, (int)w.e[j].z, (int)w.e[j].w};
 #endif
-    const mx_v8i b = {(int)e.x[i][0].x, (int)e.x[i][0].y, (int)e.x[i][0].z, (int)e.x[i][0].w, (int)e.x[i][1].x, (int)e.x[i][1].y, (int)e.x[i][1].z, (int)e.x[i][1].w};
+    const v8i b = {(int)e.x[i][0].x, (int)e.x[i][0].y, (int)e.x[i][0].z, (int)e.x[i][0].w, (int)e.x[i][1].x, (int)e.x[i][1].y, (int)e.x[i][1].z, (int)e.x[i][1].w};
     // operand formats: 0 = e4m3 (weights), 1 = e5m2 (activations)
     if constexpr (decltype(tr)::value) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, acc[i][j], 1, 0, 0, scale_x, 0, scale_w);
     else acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[i][j], 0, 1, 0, scale_w, 0, scale_x);
@@ -237,13 +196,13 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
     auto piece_off = [&](int grp) -> size_t {
       const int w = grp * 8 + g_row;
       const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-      return (size_t)row * x_pitch + (size_t)mswz(w, g_slot) * 16u;
+      return (size_t)row * x_pitch + (size_t)lds_swz(w, g_slot) * 16u;
     };
     const size_t off_a = piece_off(wave), off_b = piece_off(8);
     auto issue_A = [&](int c, int buf) {
       const unsigned char *base = xg + (size_t)c * MROW;
-      chainm_glds16(base + off_a, __builtin_amdgcn_readfirstlane(lds_base + buf * MSTG + wave * 1024));
-      if (wave == 0) chainm_glds16(base + off_b, __builtin_amdgcn_readfirstlane(lds_base + buf * MSTG + 8 * 1024));
+      glds16(base + off_a, __builtin_amdgcn_readfirstlane(lds_base + buf * MSTG + wave * 1024));
+      if (wave == 0) glds16(base + off_b, __builtin_amdgcn_readfirstlane(lds_base + buf * MSTG + 8 * 1024));
     };
     // f32 rows -> image rows [hi halves of 32 channels (slots 0-3) | x_lo8 (slots 4, 5 = lane halves 0, 1) | x_hi8 (slots 6, 7)], in place; thread (w, q)
     // converts channels 8 q .. 8 q + 7 of row w: cv_load reads its 32 bytes, cv_store writes its 16 + 8 + 8
@@ -252,8 +211,8 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
       if (tid < MWINR * 4) {
         const int w = tid >> 2, q = tid & 3;
         const unsigned char *src = lds + buf * MSTG + w * MROW;
-        cva = *reinterpret_cast<const uint4 *>(src + mswz(w, 2 * q) * 16);
-        cvb = *reinterpret_cast<const uint4 *>(src + mswz(w, 2 * q + 1) * 16);
+        cva = *reinterpret_cast<const uint4 *>(src + lds_swz(w, 2 * q) * 16);
+        cvb = *reinterpret_cast<const uint4 *>(src + lds_swz(w, 2 * q + 1) * 16);
       }
     };
     auto cv_store = [&](int buf) {
@@ -266,10 +225,10 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
         split_mx<false>(__uint_as_float(cvb.x), __uint_as_float(cvb.y), hi.z, h8b, l8b, range);
         split_mx<true>(__uint_as_float(cvb.z), __uint_as_float(cvb.w), hi.w, h8b, l8b, range);
         unsigned char *dst = lds + buf * MSTG + w * MROW;
-        *reinterpret_cast<uint4 *>(dst + mswz(w, q) * 16) = hi;
+        *reinterpret_cast<uint4 *>(dst + lds_swz(w, q) * 16) = hi;
         // byte b of an 8-bit slot of lane half lh = channel (b < 8 ? 8 lh + b : 16 + 8 lh + b - 8): the order of the lane's two half fragments
-        *reinterpret_cast<uint2 *>(dst + mswz(w, 4 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)l8a, (uint32_t)l8b);
-        *reinterpret_cast<uint2 *>(dst + mswz(w, 6 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)h8a, (uint32_t)h8b);
+        *reinterpret_cast<uint2 *>(dst + lds_swz(w, 4 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)l8a, (uint32_t)l8b);
+        *reinterpret_cast<uint2 *>(dst + lds_swz(w, 6 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)h8a, (uint32_t)h8b);
       }
     };
     // fragment offsets of pair (c, t) in the tap-major arrays of pack_tdnn_weight_frags / _mx8.  (A copy in this loop's own order - consecutive
@@ -332,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }
-    init_acc(p.first.bias + wave * 64, p.first.w_scale, MTrNo{});
+    init_acc(p.first.bias + wave * 64, p.first.w_scale, TrNo{});
     {
       uint32_t base; int sw;
       x_row(0, 0, base, sw);
@@ -396,13 +355,13 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
         if (q == 2) { whi8(wc.h0[0], wq[0].x, wq[0].y); whi8(wc.h0[1], wq[1].x, wq[1].y); }
 #endif
         if (q == 3) { en.x[1][0] = *reinterpret_cast<const uint4 *>(lds + ax0 + 32 * MROW); en.x[1][1] = *reinterpret_cast<const uint4 *>(lds + ax1 + 32 * MROW); }
-        mma_main(wc.h0, h0x, q, MTrNo{});
+        mma_main(wc.h0, h0x, q, TrNo{});
         __builtin_amdgcn_sched_barrier(0);
       }
       // phase 2: k-group 1; the rows of the next pair's k-group 0 into the registers phase 1 has just read
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        mma_main(wc.h1, h1x, q, MTrNo{});
+        mma_main(wc.h1, h1x, q, TrNo{});
         if (q == 0) { h0x[0] = *reinterpret_cast<const uint4 *>(lds + ah0); h0x[1] = *reinterpret_cast<const uint4 *>(lds + ah0 + 32 * MROW); }
 #if CHAINM_WHI8_REG
         if (q == 1) { whi8(wc.h1[0], wq[0].z, wq[0].w); whi8(wc.h1[1], wq[1].z, wq[1].w); }
@@ -413,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
       // phase 3: the corrections; the rows of the next pair's k-group 1
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        mma_mx(wc, ec, q, MTrNo{});
+        mma_mx(wc, ec, q, TrNo{});
         if (q == 0) { h1x[0] = *reinterpret_cast<const uint4 *>(lds + ah1); h1x[1] = *reinterpret_cast<const uint4 *>(lds + ah1 + 32 * MROW); }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -567,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
     stage_params(L);
     const unsigned char *wbh = reinterpret_cast<const unsigned char *>(L.wfrag) + (size_t)(wave * 2) * ((size_t)(MN / 16) * 1024);
     const unsigned char *wb8 = reinterpret_cast<const unsigned char *>(L.w8) + (size_t)(wave * 2) * ((size_t)(MN / 32) * 1024);
-    yloop(wbh, wb8, (size_t)(L.cout_pad / 32) * ((size_t)(MN / 32) * 1024), L.bias + wave * 64, L.w_scale, MTrNo{});
+    yloop(wbh, wb8, (size_t)(L.cout_pad / 32) * ((size_t)(MN / 32) * 1024), L.bias + wave * 64, L.w_scale, TrNo{});
     stamp();                                                     // 5: a middle layer's K loop
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();          // nobody reads the old Y any more (and the staged constants are visible)
@@ -585,84 +544,15 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainm_kernel(const TdnnChainPara
     const float act_lo = L.relu ? 0.0f : -INFINITY;
     const float unscale = 1.0f / L.w_scale;
     const int tile = m0 >> 6;
-    int first_seg = -1;
-#pragma unroll
-    for (int k = 0; k < kHalo + 1; ++k)
-      if (first_seg < 0 && m0 + k < p.rows) first_seg = p.row_seg[m0 + k];
+    const int first_seg = pool_first_seg(p, m0);
     const int rowseg = p.row_seg[m0 + lane];                  // the tile's 64 rows: lane l = row l
 #pragma unroll 1
     for (int cb = wave * 64; cb < L.cout_pad; cb += 512) {
       const unsigned char *wbh = reinterpret_cast<const unsigned char *>(L.wfrag) + (size_t)(cb / 32) * ((size_t)(MN / 16) * 1024);
       const unsigned char *wb8 = reinterpret_cast<const unsigned char *>(L.w8) + (size_t)(cb / 32) * ((size_t)(MN / 32) * 1024);
-      yloop(wbh, wb8, (size_t)(L.cout_pad / 32) * ((size_t)(MN / 32) * 1024), L.bias + cb, L.w_scale, MTrYes{});
+      yloop(wbh, wb8, (size_t)(L.cout_pad / 32) * ((size_t)(MN / 32) * 1024), L.bias + cb, L.w_scale, TrYes{});
       stamp();                                                   // 7, 9, 11: a unit's K loop
-      // Pooling epilogue, registers only (kernels_tdnn_chainx.hip, the same arithmetic): acc[i][j][r] = channel cb + j*32 + lr, frame
-      // i*32 + 8 (r >> 2) + 4 lh + (r & 3); a lane sums its own frames per utterance about the pivot of its FIRST frame of that utterance,
-      // the two lane halves publish P[tile of 64 rows][segment slot][lh][3 = sum (u - pv), sum (u - pv)^2, pv][channel] with the BN scale
-      // applied at publication; pool_finish_kernel merges the parts and adds the BN shift.
-      const float sc[2] = {L.scale != nullptr ? L.scale[cb + lr] : 1.0f, L.scale != nullptr ? L.scale[cb + 32 + lr] : 1.0f};
-      float ps[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f}, pv[2] = {0.f, 0.f};
-      int cur_seg = -1;                      // uniform: all lanes walk the utterances of the tile together
-      bool have = false;                     // per lane: pv is a frame of cur_seg (the lane has had a frame of it in this tile)
-      auto publish = [&]() {
-        const int slot = cur_seg - first_seg;
-        if (cur_seg >= 0 && slot >= 0 && slot < p.pool_slots) {
-          float *dst = p.pool_partial + ((size_t)((tile * p.pool_slots + slot) * 2 + lh) * 3) * p.ld_partial + cb + lr;
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            if (cb + j * 32 + lr < p.ld_partial) {
-              dst[j * 32] = ps[j] * sc[j];
-              dst[j * 32 + p.ld_partial] = pq[j] * sc[j] * sc[j];
-              dst[j * 32 + 2 * p.ld_partial] = pv[j] * sc[j];
-            }
-        }
-      };
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int shift = i * 32;
-        uint32_t rem = (uint32_t)(__builtin_amdgcn_ballot_w64(rowseg >= 0) >> shift);       // rows of the fragment that belong to an utterance
-        if (rem == 0) continue;                                                              // gap rows only
-        float u[2][16];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) u[j][r] = max_lo(acc[i][j][r] * unscale, act_lo);
-        while (rem != 0) {                                       // one run per utterance present, in row order
-          const int sg = __builtin_amdgcn_readlane(rowseg, shift + __builtin_ctz(rem));
-          const uint32_t bits = (uint32_t)(__builtin_amdgcn_ballot_w64(rowseg == sg) >> shift) & rem;
-          rem &= ~bits;
-          const bool fresh = sg != cur_seg;
-          if (fresh) {
-            publish();
-            cur_seg = sg;
-            have = false;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { ps[j] = 0.0f; pq[j] = 0.0f; }
-          }
-          // register r of this lane holds frame 8 (r >> 2) + 4 lh + (r & 3) -> bit r of the lane's mask
-          const uint32_t x = bits >> (4 * lh);
-          const uint32_t lm = (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
-          const bool need = !have && lm != 0;                    // (the stale-pivot rule of round 5: tests/test_gpu_xvector.py::test_pooled_moments_ignore_the_neighbour)
-          if (__builtin_amdgcn_ballot_w64(need) != 0) {
-            const int rsel = need ? __builtin_ctz(lm) : 16;
-#pragma unroll
-            for (int r = 15; r >= 0; --r) {
-              const bool hit = rsel == r;
-              pv[0] = hit ? u[0][r] : pv[0];
-              pv[1] = hit ? u[1][r] : pv[1];
-            }
-            have = have || need;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int tm = (int)(lm << (31 - r)) >> 31;          // all ones where the frame is in the run
-            const float da = __int_as_float(__float_as_int(u[0][r] - pv[0]) & tm), db = __int_as_float(__float_as_int(u[1][r] - pv[1]) & tm);
-            ps[0] += da; pq[0] = fmaf(da, da, pq[0]);
-            ps[1] += db; pq[1] = fmaf(db, db, pq[1]);
-          }
-        }
-      }
-      publish();
+      chain64_pool_epilogue(acc, p, L, cb, tile, first_seg, rowseg, lr, lh, unscale, act_lo);      // chain_pool.h, shared with kernels_tdnn_chainx.hip
       stamp();                                                   // 8, 10, 12: its pooling epilogue
     }
   }

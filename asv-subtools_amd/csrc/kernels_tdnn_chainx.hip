@@ -17,7 +17,8 @@
 // instructions of the previous one.  One workgroup (512 threads, 160 KiB of LDS) per CU.
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "chain_pool.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -34,25 +35,6 @@ constexpr int XPAR = 2 * YIMG;             // bias | scale | shift of the layer 
 constexpr int CHAINX_LDS = 2 * YIMG + 8192;
 static_assert(4 * XSTG <= YIMG, "layer A's stages and images live inside the Y region");
 static_assert(CHAINX_LDS <= 163840, "160 KiB of LDS per CU");
-
-typedef __attribute__((address_space(3))) unsigned char chainx_lds_byte;
-struct XTrNo { static constexpr bool value = false; };
-struct XTrYes { static constexpr bool value = true; };
-
-__device__ __forceinline__ int wswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void chainx_glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
 
 // two f32 -> hi pair + lo pair of the 16-bit type (kernels_tdnn_x3.hip x3_split)
 template <int ET>
@@ -79,7 +61,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainx_kernel(const TdnnChainPara
   const int lr = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * XM;
   uint32_t range = 0u;                      // range watch of the half split (device_utils.h): layer A's window and the resident tiles
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(chainx_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   float *par = reinterpret_cast<float *>(lds + XPAR);
   const uint32_t lane16 = (uint32_t)lane * 16u;
 
@@ -143,29 +125,29 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainx_kernel(const TdnnChainPara
     auto piece_off = [&](int grp) -> size_t {
       const int w = grp * 8 + g_row;
       const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-      return (size_t)row * x_pitch + (size_t)wswz(w, g_slot) * 16u;
+      return (size_t)row * x_pitch + (size_t)lds_swz(w, g_slot) * 16u;
     };
     const size_t off_a = piece_off(wave), off_b = piece_off(8);
     auto issue_A = [&](int c) {
       const unsigned char *base = xg + (size_t)c * XROW;
-      chainx_glds16(base + off_a, __builtin_amdgcn_readfirstlane(lds_base + (c & 1) * XSTG + wave * 1024));
-      if (wave == 0) chainx_glds16(base + off_b, __builtin_amdgcn_readfirstlane(lds_base + (c & 1) * XSTG + 8 * 1024));
+      glds16(base + off_a, __builtin_amdgcn_readfirstlane(lds_base + (c & 1) * XSTG + wave * 1024));
+      if (wave == 0) glds16(base + off_b, __builtin_amdgcn_readfirstlane(lds_base + (c & 1) * XSTG + 8 * 1024));
     };
     // f32 stage c & 1 -> image c & 1 (at 2 * XSTG): row = [hi of 32 channels (4 slots) | lo (4 slots)]
     auto convert = [&](int c) {
       if (tid < XWINR * 4) {
         const int w = tid >> 2, q = tid & 3;
         const unsigned char *src = lds + (c & 1) * XSTG + w * XROW;
-        const uint4 a = *reinterpret_cast<const uint4 *>(src + wswz(w, 2 * q) * 16);
-        const uint4 b = *reinterpret_cast<const uint4 *>(src + wswz(w, 2 * q + 1) * 16);
+        const uint4 a = *reinterpret_cast<const uint4 *>(src + lds_swz(w, 2 * q) * 16);
+        const uint4 b = *reinterpret_cast<const uint4 *>(src + lds_swz(w, 2 * q + 1) * 16);
         uint4 hi, lo;
         split2<ET>(__uint_as_float(a.x), __uint_as_float(a.y), hi.x, lo.x, range);
         split2<ET>(__uint_as_float(a.z), __uint_as_float(a.w), hi.y, lo.y, range);
         split2<ET>(__uint_as_float(b.x), __uint_as_float(b.y), hi.z, lo.z, range);
         split2<ET>(__uint_as_float(b.z), __uint_as_float(b.w), hi.w, lo.w, range);
         unsigned char *dst = lds + (2 + (c & 1)) * XSTG + w * XROW;
-        *reinterpret_cast<uint4 *>(dst + wswz(w, q) * 16) = hi;
-        *reinterpret_cast<uint4 *>(dst + wswz(w, 4 + q) * 16) = lo;
+        *reinterpret_cast<uint4 *>(dst + lds_swz(w, q) * 16) = hi;
+        *reinterpret_cast<uint4 *>(dst + lds_swz(w, 4 + q) * 16) = lo;
       }
     };
     const size_t frag_stride = (size_t)n_taps * nkg * 1024;
@@ -200,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainx_kernel(const TdnnChainPara
     asm volatile("" ::: "memory");
     if (nchunks > 2) issue_A(2);
     if (nchunks > 1) convert(1);
-    init_acc(p.first.bias + wave * 64, p.first.w_scale, XTrNo{});
+    init_acc(p.first.bias + wave * 64, p.first.w_scale, TrNo{});
     {
       uint32_t ah, al;
       x_addr(0, 0, 0, ah, al);
@@ -240,8 +222,8 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainx_kernel(const TdnnChainPara
         if (pr == 2 && enter && c + 3 < nchunks) issue_A(c + 3);
         if (pr == 2) { xn.h[0] = *reinterpret_cast<const uint4 *>(lds + ah); xn.h[1] = *reinterpret_cast<const uint4 *>(lds + ah + 32 * XROW); }
         if (pr == 3) { xn.l[0] = *reinterpret_cast<const uint4 *>(lds + al); xn.l[1] = *reinterpret_cast<const uint4 *>(lds + al + 32 * XROW); }
-        mma1(xc, wc, 2 * pr, XTrNo{});
-        mma1(xc, wc, 2 * pr + 1, XTrNo{});
+        mma1(xc, wc, 2 * pr, TrNo{});
+        mma1(xc, wc, 2 * pr + 1, TrNo{});
         __builtin_amdgcn_sched_barrier(0);
       }
       c = c2; t = t2;
@@ -348,7 +330,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainx_kernel(const TdnnChainPara
     const size_t frag_stride = (size_t)(XN / 16) * 1024;
     const unsigned char *wbh = reinterpret_cast<const unsigned char *>(L.wfrag) + (size_t)(wave * 2) * frag_stride;
     const unsigned char *wbl = reinterpret_cast<const unsigned char *>(L.wlo) + (size_t)(wave * 2) * frag_stride;
-    yloop(wbh, wbl, L.bias + wave * 64, L.w_scale, XTrNo{});
+    yloop(wbh, wbl, L.bias + wave * 64, L.w_scale, TrNo{});
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();          // nobody reads the old Y any more (and the staged constants are visible)
     asm volatile("" ::: "memory");
@@ -364,89 +346,15 @@ __global__ __launch_bounds__(512, 2) void tdnn_chainx_kernel(const TdnnChainPara
     const float act_lo = L.relu ? 0.0f : -INFINITY;
     const float unscale = 1.0f / L.w_scale;
     const int tile = m0 >> 6;
-    int first_seg = -1;
-#pragma unroll
-    for (int k = 0; k < kHalo + 1; ++k)
-      if (first_seg < 0 && m0 + k < p.rows) first_seg = p.row_seg[m0 + k];
+    const int first_seg = pool_first_seg(p, m0);
     const int rowseg = p.row_seg[m0 + lane];                  // the tile's 64 rows: lane l = row l
     const size_t frag_stride = (size_t)(XN / 16) * 1024;
 #pragma unroll 1
     for (int cb = wave * 64; cb < L.cout_pad; cb += 512) {
       const unsigned char *wbh = reinterpret_cast<const unsigned char *>(L.wfrag) + (size_t)(cb / 32) * frag_stride;
       const unsigned char *wbl = reinterpret_cast<const unsigned char *>(L.wlo) + (size_t)(cb / 32) * frag_stride;
-      yloop(wbh, wbl, L.bias + cb, L.w_scale, XTrYes{});
-      // Pooling epilogue, registers only (kernels_tdnn_chain.hip): acc[i][j][r] = channel cb + j*32 + lr, frame i*32 + 8 (r >> 2) +
-      // 4 lh + (r & 3); a lane sums its own frames per utterance about the pivot of its first frame, the two lane halves publish
-      //   P[tile of 64 rows][segment slot][lh][3 = sum (u - pv), sum (u - pv)^2, pv][channel]
-      // with the BN scale applied at publication; pool_finish_kernel merges the parts and adds the BN shift.
-      const float sc[2] = {L.scale != nullptr ? L.scale[cb + lr] : 1.0f, L.scale != nullptr ? L.scale[cb + 32 + lr] : 1.0f};
-      float ps[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f}, pv[2] = {0.f, 0.f};
-      int cur_seg = -1;                      // uniform: all lanes walk the utterances of the tile together
-      bool have = false;                     // per lane: pv is a frame of cur_seg (the lane has had a frame of it in this tile)
-      auto publish = [&]() {
-        const int slot = cur_seg - first_seg;
-        if (cur_seg >= 0 && slot >= 0 && slot < p.pool_slots) {
-          float *dst = p.pool_partial + ((size_t)((tile * p.pool_slots + slot) * 2 + lh) * 3) * p.ld_partial + cb + lr;
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            if (cb + j * 32 + lr < p.ld_partial) {
-              dst[j * 32] = ps[j] * sc[j];
-              dst[j * 32 + p.ld_partial] = pq[j] * sc[j] * sc[j];
-              dst[j * 32 + 2 * p.ld_partial] = pv[j] * sc[j];
-            }
-        }
-      };
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int shift = i * 32;
-        uint32_t rem = (uint32_t)(__builtin_amdgcn_ballot_w64(rowseg >= 0) >> shift);       // rows of the fragment that belong to an utterance
-        if (rem == 0) continue;                                                              // gap rows only
-        float u[2][16];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) u[j][r] = max_lo(acc[i][j][r] * unscale, act_lo);
-        while (rem != 0) {                                       // one run per utterance present, in row order
-          const int sg = __builtin_amdgcn_readlane(rowseg, shift + __builtin_ctz(rem));
-          const uint32_t bits = (uint32_t)(__builtin_amdgcn_ballot_w64(rowseg == sg) >> shift) & rem;
-          rem &= ~bits;
-          const bool fresh = sg != cur_seg;
-          if (fresh) {
-            publish();
-            cur_seg = sg;
-            have = false;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { ps[j] = 0.0f; pq[j] = 0.0f; }
-          }
-          // register r of this lane holds frame 8 (r >> 2) + 4 lh + (r & 3) -> bit r of the lane's mask
-          const uint32_t x = bits >> (4 * lh);
-          const uint32_t lm = (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
-          // pivot = the lane's FIRST frame of the utterance, in whichever fragment of the tile that frame lies.  (Until round 5 the
-          // pivot was only taken in the utterance's first fragment: a lane half without a frame there - an utterance starting in
-          // the last rows of a fragment - kept the previous utterance's pivot for the rest of the tile.  Harmless between
-          // utterances of like scale, but next to one whose activations are 1e5 x larger the sums about that pivot cancelled:
-          // an embedding that depended on its batch neighbour, tests/test_gpu_xvector.py::test_pooled_moments_ignore_the_neighbour.)
-          const bool need = !have && lm != 0;
-          if (__builtin_amdgcn_ballot_w64(need) != 0) {
-            const int rsel = need ? __builtin_ctz(lm) : 16;
-#pragma unroll
-            for (int r = 15; r >= 0; --r) {
-              const bool hit = rsel == r;
-              pv[0] = hit ? u[0][r] : pv[0];
-              pv[1] = hit ? u[1][r] : pv[1];
-            }
-            have = have || need;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int tm = (int)(lm << (31 - r)) >> 31;          // all ones where the frame is in the run
-            const float da = __int_as_float(__float_as_int(u[0][r] - pv[0]) & tm), db = __int_as_float(__float_as_int(u[1][r] - pv[1]) & tm);
-            ps[0] += da; pq[0] = fmaf(da, da, pq[0]);
-            ps[1] += db; pq[1] = fmaf(db, db, pq[1]);
-          }
-        }
-      }
-      publish();
+      yloop(wbh, wbl, L.bias + cb, L.w_scale, TrYes{});
+      chain64_pool_epilogue(acc, p, L, cb, tile, first_seg, rowseg, lr, lh, unscale, act_lo);      // chain_pool.h
     }
   }
   x3_publish_range(range, p.status);

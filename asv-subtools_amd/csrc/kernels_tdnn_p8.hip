@@ -42,7 +42,8 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "device_utils.h"
+#define ASV_GLDS_CLOBBER_M0      // glds16_s_m0: this unit is built with -Wno-inline-asm (Makefile)
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -53,20 +54,6 @@ constexpr int P8_BUF = 4 * P8_HALF;                 // 64 KiB per K-tile buffer
 constexpr int P8_PARAM_OFF = 2 * P8_BUF;
 constexpr int P8_LDS_BYTES = 2 * P8_BUF + 3 * 256 * 4;
 constexpr int P8_ROWB = 128;
-
-typedef __attribute__((address_space(3))) unsigned char p8_lds_byte;
-
-// one LDS-DMA instruction: 64 lanes x 16 bytes from (scalar base + per-lane 32-bit byte offset) to LDS [M0 .. M0 + 1024).
-// M0 is declared clobbered instead of saved and restored (nothing else in this kernel reads it: two SALU operations less per piece).
-__device__ __forceinline__ void p8_glds(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory", "m0");
-}
 
 // VAR (measurement variants of the developer build; 0 = the production kernel):
 //   1 no stagger between the wave rows    2 no s_setprio around the MFMA clusters (+0 ... +5 % with it)    3 neither
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
   const int cin_pad = p.cin_pad;
   const int n_taps = ONE_TAP ? 1 : p.n_taps;
   const uint32_t w_pitch = (uint32_t)n_taps * (uint32_t)cin_pad * 2u;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(p8_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   const int nkt = (cin_pad / 64) * n_taps;
 
   // per-channel epilogue constants (bias | scale | shift of the tile's 256 channels) -> LDS by LDS-DMA, one 1 KiB piece each, issued by
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
     if (wave < 3) {
       const float *src = (wave == 0) ? p.bias : (wave == 1 ? p.scale : p.shift);
       if (src != nullptr) {
-        p8_glds(src + n0, (uint32_t)lane * 16u, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)P8_PARAM_OFF + (uint32_t)wave * 1024u));
+        glds16_s_m0(src + n0, (uint32_t)lane * 16u, __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)P8_PARAM_OFF + (uint32_t)wave * 1024u));
       } else {
         const float dflt = (wave == 1) ? 1.0f : 0.0f;
         *reinterpret_cast<float4 *>(lds_par + wave * 256 + lane * 4) = make_float4(dflt, dflt, dflt, dflt);
@@ -155,19 +142,19 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
       const unsigned char *base = xg + (size_t)c * 128;
       if (ONE_TAP) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) p8_glds(base, a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+        for (int i = 0; i < 2; ++i) glds16_s_m0(base, a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
       } else {
         const int d = __builtin_amdgcn_readlane(v_taps, t) + (which == 3 ? 64 : 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int row = min(max(a_row[i] + d, 0), last_row);
-          p8_glds(base, (uint32_t)row * x_pitch + a_slot[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+          glds16_s_m0(base, (uint32_t)row * x_pitch + a_slot[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
         }
       }
     } else {
       const unsigned char *base = wg + ((size_t)t * cin_pad + (size_t)c * 64) * 2 + (which == 2 ? (size_t)32 * w_pitch : 0);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) p8_glds(base, b_off[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+      for (int i = 0; i < 2; ++i) glds16_s_m0(base, b_off[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
     }
   };
 
@@ -432,7 +419,6 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
   uint32_t vmask = 0;                                     // bit i: this lane's frame of m-fragment i is a real frame
 #pragma unroll
   for (int i = 0; i < 4; ++i) vmask |= ((p.row_valid[(m0 + wm * 128 + i * 32) >> 5] >> lr) & 1u) << i;
-  auto swz = [](int row, int slot) { return slot ^ ((row >> 1) & 7); };
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -456,7 +442,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
         pk.x = valid ? pk.x : 0u;                  // gap rows are zeros: on the packed pairs, 2 selects per 4 values
         pk.y = valid ? pk.y : 0u;
         // odd rows keep their two 8-byte halves swapped so rows r, r+1 (same slot) hit different banks
-        *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + swz(frow, slot) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
+        *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + lds_swz(frow, slot) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
       }
     }
   }
@@ -467,7 +453,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
       const int piece = it * 64 + lane, frow = piece >> 3, slot = piece & 7;
-      uint4 v = *reinterpret_cast<const uint4 *>(scr + frow * P8_ROWB + swz(frow, slot) * 16);
+      uint4 v = *reinterpret_cast<const uint4 *>(scr + frow * P8_ROWB + lds_swz(frow, slot) * 16);
       if (frow & 1) v = make_uint4(v.z, v.w, v.x, v.y);
       const int ch = n0 + wn * 64 + slot * 8;
       const int row = m0 + wm * 128 + frow;
@@ -511,7 +497,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
   const int cin_pad = p.cin_pad;
   const int n_taps = ONE_TAP ? 1 : p.n_taps;
   const uint32_t w_pitch = (uint32_t)n_taps * (uint32_t)cin_pad * 2u;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(p8_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   const int nkt = (cin_pad / 64) * n_taps;
   const int last_row = p.rows - 1;
   const int g_row = lane >> 3, g_slot = lane & 7;
@@ -546,19 +532,19 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
       const unsigned char *base = xg + (size_t)c * 128;
       if (ONE_TAP) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) p8_glds(base, T.a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+        for (int i = 0; i < 2; ++i) glds16_s_m0(base, T.a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
       } else {
         const int d = __builtin_amdgcn_readlane(v_taps, t) + (which == 3 ? 64 : 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int row = min(max(T.a_row[i] + d, 0), last_row);
-          p8_glds(base, (uint32_t)row * x_pitch + T.a_slot[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+          glds16_s_m0(base, (uint32_t)row * x_pitch + T.a_slot[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
         }
       }
     } else {
       const unsigned char *base = wg + ((size_t)t * cin_pad + (size_t)c * 64) * 2 + (which == 2 ? (size_t)32 * w_pitch : 0);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) p8_glds(base, T.b_off[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+      for (int i = 0; i < 2; ++i) glds16_s_m0(base, T.b_off[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
     }
   };
   // bias | scale | shift of the tile's 256 channels and the validity words of its 256 rows -> parameter slot `slot`: one piece each
@@ -568,14 +554,14 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
     if (wave < 3) {
       const float *src = (wave == 0) ? p.bias : (wave == 1 ? p.scale : p.shift);
       if (src != nullptr) {
-        p8_glds(src + T.n0, (uint32_t)lane * 16u, __builtin_amdgcn_readfirstlane(dst));
+        glds16_s_m0(src + T.n0, (uint32_t)lane * 16u, __builtin_amdgcn_readfirstlane(dst));
       } else {
         const float dflt = (wave == 1) ? 1.0f : 0.0f;
         *reinterpret_cast<float4 *>(lds + 2 * P8_BUF + slot * P8P_PAR_SLOT + wave * 1024 + lane * 16) = make_float4(dflt, dflt, dflt, dflt);
       }
     } else if (wave == 3) {
       // 8 words = 32 bytes: lanes 0 and 1 fetch them, the others re-read the first 16 bytes (valid memory; their LDS bytes are never used)
-      p8_glds(p.row_valid + (T.m0 >> 5), lane < 2 ? (uint32_t)lane * 16u : 0u, __builtin_amdgcn_readfirstlane(dst));
+      glds16_s_m0(p.row_valid + (T.m0 >> 5), lane < 2 ? (uint32_t)lane * 16u : 0u, __builtin_amdgcn_readfirstlane(dst));
     }
   };
 
@@ -593,7 +579,6 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
     asm volatile("" ::: "memory");
   };
   auto kt_ct = [&](int kt, int &c, int &t) { c = kt / n_taps; t = kt - c * n_taps; };
-  auto swz = [](int row, int slot) { return slot ^ ((row >> 1) & 7); };
   const float act_lo = (p.act1 == ASV_ACT_RELU) ? 0.0f : -INFINITY;
   unsigned char *yg = reinterpret_cast<unsigned char *>(p.y);
   const size_t y_pitch = (size_t)p.ldy * 2;
@@ -723,14 +708,14 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
               pk.y = pack_h16x2<ET>(y[2], y[3]);
               pk.x = valid ? pk.x : 0u;
               pk.y = valid ? pk.y : 0u;
-              *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + swz(frow, sl) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
+              *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + lds_swz(frow, sl) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
             }
           }
         }
 #pragma unroll
         for (int s8 = 0; s8 < 8; ++s8) {
           const int piece = s8 * 64 + lane, frow = piece >> 3, sl = piece & 7;
-          uint4 v = *reinterpret_cast<const uint4 *>(scr + frow * P8_ROWB + swz(frow, sl) * 16);
+          uint4 v = *reinterpret_cast<const uint4 *>(scr + frow * P8_ROWB + lds_swz(frow, sl) * 16);
           if (frow & 1) v = make_uint4(v.z, v.w, v.x, v.y);
           const int ch = cur.n0 + wn * 64 + sl * 8;
           const int row = cur.m0 + wm * 128 + h * 64 + frow;

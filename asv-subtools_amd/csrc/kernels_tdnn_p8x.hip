@@ -24,7 +24,8 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "device_utils.h"
+#define ASV_GLDS_CLOBBER_M0      // glds16_s_m0: this unit is built with -Wno-inline-asm (Makefile)
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -35,18 +36,6 @@ constexpr int PX_BUF = 4 * PX_HALF;
 constexpr int PX_PAR_SLOT = 4096;
 constexpr int PX_LDS_BYTES = 2 * PX_BUF + 2 * PX_PAR_SLOT;
 constexpr int PX_ROWB = 128;
-
-typedef __attribute__((address_space(3))) unsigned char px_lds_byte;
-
-__device__ __forceinline__ void px_glds(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory", "m0");
-}
 
 template <int XET, bool ONE_TAP>
 __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8x_kernel(const TdnnKernelParams p, int m_tiles, int n_tiles) {
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8x_kernel(const TdnnKernelP
   const int nchunks = p.cin_pad / 32;
   const int n_taps = ONE_TAP ? 1 : p.n_taps;
   const uint32_t w_pitch = (uint32_t)n_taps * (uint32_t)nchunks * 128u;      // bytes per output channel
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(px_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   const int nkt = nchunks * n_taps;
   const int last_row = p.rows - 1;
   const int g_row = lane >> 3, g_slot = lane & 7;
@@ -99,19 +88,19 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8x_kernel(const TdnnKernelP
       const unsigned char *base = xg + (size_t)c * 128;
       if (ONE_TAP) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) px_glds(base, T.a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+        for (int i = 0; i < 2; ++i) glds16_s_m0(base, T.a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
       } else {
         const int d = __builtin_amdgcn_readlane(v_taps, t) + (which == 3 ? 64 : 0);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int row = min(max(T.a_row[i] + d, 0), last_row);
-          px_glds(base, (uint32_t)row * x_pitch + T.a_slot[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+          glds16_s_m0(base, (uint32_t)row * x_pitch + T.a_slot[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
         }
       }
     } else {
       const unsigned char *base = wg + ((size_t)t * nchunks + (size_t)c) * 128 + (which == 2 ? (size_t)32 * w_pitch : 0);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) px_glds(base, T.b_off[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+      for (int i = 0; i < 2; ++i) glds16_s_m0(base, T.b_off[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
     }
   };
   auto stage_tile_params = [&](const TileAddr &T, int slot) {
@@ -119,13 +108,13 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8x_kernel(const TdnnKernelP
     if (wave < 3) {
       const float *src = (wave == 0) ? p.bias : (wave == 1 ? p.scale : p.shift);
       if (src != nullptr) {
-        px_glds(src + T.n0, (uint32_t)lane * 16u, __builtin_amdgcn_readfirstlane(dst));
+        glds16_s_m0(src + T.n0, (uint32_t)lane * 16u, __builtin_amdgcn_readfirstlane(dst));
       } else {
         const float dflt = (wave == 1) ? 1.0f : 0.0f;
         *reinterpret_cast<float4 *>(lds + 2 * PX_BUF + slot * PX_PAR_SLOT + wave * 1024 + lane * 16) = make_float4(dflt, dflt, dflt, dflt);
       }
     } else if (wave == 3) {
-      px_glds(p.row_valid + (T.m0 >> 5), lane < 2 ? (uint32_t)lane * 16u : 0u, __builtin_amdgcn_readfirstlane(dst));
+      glds16_s_m0(p.row_valid + (T.m0 >> 5), lane < 2 ? (uint32_t)lane * 16u : 0u, __builtin_amdgcn_readfirstlane(dst));
     }
   };
 

@@ -21,7 +21,7 @@
 //     LDS-staged 16-byte stores).
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -58,38 +58,6 @@ template <int WM> struct Geom3 {
   static constexpr int LDS_BYTES = RING_BYTES + 3 * 256 * 4;
   static_assert(WAVES * SCRATCH <= RING_BYTES, "epilogue scratch must fit in the ring");
 };
-
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
-
-__device__ __forceinline__ int swz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-// one LDS-DMA instruction (see kernels_tdnn_v2.hip for why this is inline asm)
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-// same with a scalar base + 32-bit per-lane byte offset (no 64-bit VALU address arithmetic per piece)
-__device__ __forceinline__ void glds16_s(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 
 // ABL: 0 full, 1 full + short loop for a partial last chunk (cin % 64 != 0), 2 MFMA only (no loads of any kind in the loop), 4 no epilogue stores,
 //      5 full + per-workgroup phase timestamps into p.partial, 6 MFMA only + timestamps
@@ -162,7 +130,7 @@ __global__ __launch_bounds__(Geom3<WM>::WAVES * 64, WM == 0 ? 3 : 2) void tdnn_g
     const int grp = min(wave + i * G::WAVES, A_GROUPS - 1);
     const int w = grp * 8 + g_row;
     const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-    a_off[i] = (uint32_t)row * (uint32_t)x_pitch + (uint32_t)swz(w, g_slot) * 16u;
+    a_off[i] = (uint32_t)row * (uint32_t)x_pitch + (uint32_t)lds_swz(w, g_slot) * 16u;
   }
   auto issue_A = [&](int c, int st) {
     const unsigned char *base = xg + (size_t)c * (BK * 2);
@@ -175,7 +143,7 @@ __global__ __launch_bounds__(Geom3<WM>::WAVES * 64, WM == 0 ? 3 : 2) void tdnn_g
         glds16_s(base, a_off[i], dst);
       } else {
         const int w = grp * 8 + g_row;
-        const bool ok = c * BK + swz(w, g_slot) * 8 < p.cin_pad;
+        const bool ok = c * BK + lds_swz(w, g_slot) * 8 < p.cin_pad;
         glds16(ok ? base + a_off[i] : zero, dst);
       }
     }
@@ -217,12 +185,12 @@ __global__ __launch_bounds__(Geom3<WM>::WAVES * 64, WM == 0 ? 3 : 2) void tdnn_g
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
       const int w = wm * (MF * 32) + i * 32 + lr + kHalo + d;
-      f.x[i] = *reinterpret_cast<const uint4 *>(Ab + w * ROWB + swz(w, slot) * 16);
+      f.x[i] = *reinterpret_cast<const uint4 *>(Ab + w * ROWB + lds_swz(w, slot) * 16);
     }
   };
   auto load_x1 = [&](const unsigned char *Ab, int d, int kg, int i, XFrags &f) {
     const int w = wm * (MF * 32) + i * 32 + lr + kHalo + d;
-    f.x[i] = *reinterpret_cast<const uint4 *>(Ab + w * ROWB + swz(w, kg * 2 + lh) * 16);
+    f.x[i] = *reinterpret_cast<const uint4 *>(Ab + w * ROWB + lds_swz(w, kg * 2 + lh) * 16);
   };
   auto mma2 = [&](const XFrags &f, int kg, int j, int i0) {
 #pragma unroll
@@ -387,7 +355,7 @@ __global__ __launch_bounds__(Geom3<WM>::WAVES * 64, WM == 0 ? 3 : 2) void tdnn_g
     const float act_lo = (p.act1 == ASV_ACT_RELU) ? 0.0f : -INFINITY;
     const int rbase_w = m0 + wm * 128;
     const int half = rbase_w >> 7;
-    int first_seg = -1;
+    int first_seg = -1;                              // (the twin of chain_pool.h pool_first_seg, on TdnnKernelParams: change both together)
 #pragma unroll
     for (int k = 0; k < kHalo + 1; ++k)
       if (first_seg < 0 && rbase_w + k < p.rows) first_seg = p.row_seg[rbase_w + k];
@@ -537,7 +505,7 @@ __global__ __launch_bounds__(Geom3<WM>::WAVES * 64, WM == 0 ? 3 : 2) void tdnn_g
           pk.y = valid ? pk.y : 0u;
         }
         // odd rows keep their two 8-byte halves swapped so rows r, r+1 (same slot) hit different banks
-        *reinterpret_cast<uint2 *>(scr + frow * ROWB + swz(frow, slot) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
+        *reinterpret_cast<uint2 *>(scr + frow * ROWB + lds_swz(frow, slot) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
       }
     }
   }
@@ -548,7 +516,7 @@ __global__ __launch_bounds__(Geom3<WM>::WAVES * 64, WM == 0 ? 3 : 2) void tdnn_g
 #pragma unroll
     for (int it = 0; it < MF * 4; ++it) {
       const int piece = it * 64 + lane, frow = piece >> 3, slot = piece & 7;
-      uint4 v = *reinterpret_cast<const uint4 *>(scr + frow * ROWB + swz(frow, slot) * 16);
+      uint4 v = *reinterpret_cast<const uint4 *>(scr + frow * ROWB + lds_swz(frow, slot) * 16);
       if (frow & 1) v = make_uint4(v.z, v.w, v.x, v.y);
       const int ch = n0 + wn * 64 + slot * 8;
       const int row = m0 + wm * (MF * 32) + frow;

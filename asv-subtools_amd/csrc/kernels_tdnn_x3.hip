@@ -11,7 +11,7 @@
 //
 // Structure = kernels_tdnn_v3.hip with smaller pieces:
 //   * the f32 feature window of a 32-channel chunk (72 frames x 128 B, shared by all taps) goes through a 4-stage
-//     LDS ring by LDS-DMA (global_load_lds_dwordx4, XOR-swizzled 16-byte slots, one barrier per chunk);
+//     LDS ring by LDS-DMA (lds_dma.h glds16, XOR-swizzled 16-byte slots, one barrier per chunk);
 //   * a lane's 8 consecutive k values are two ds_read_b128; the hi / lo split runs on the VALU
 //     (v_cvt_pk_bf16_f32: hi; x - hi is exact in f32; v_cvt_pk_bf16_f32 again: lo) next to the MFMAs of the
 //     previous k-group - the matrix and vector pipes issue independently;
@@ -26,7 +26,7 @@
 // 512 -> 1500 layer moves 1.05 GB per launch).  The next step for this mode is the 128-row wave tile of kernels_tdnn_v3.hip.
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -53,23 +53,6 @@ template <int MF> struct X3Geom {
   static_assert(4 * 32 * XSPITCH * 4 <= RING, "epilogue scratch must fit in the ring");
 };
 static_assert(XBN == kBigTileN, "weight padding must match the N tile");
-
-typedef __attribute__((address_space(3))) unsigned char x3_lds_byte;
-
-__device__ __forceinline__ int xswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void x3_glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
 
 // X3Frag / x3_split (8 f32 -> the hi and lo halves in the 16-bit type): device_utils.h, shared with kernels_conv2d_x3.hip
 
@@ -100,7 +83,7 @@ __global__ __launch_bounds__(256, MF == 2 ? 3 : 2) void tdnn_gemm_x3_kernel(cons
   const unsigned char *xg = reinterpret_cast<const unsigned char *>(p.x);
   const unsigned char *zero = reinterpret_cast<const unsigned char *>(p.zero16);
   const size_t x_pitch = (size_t)p.ldx * 4;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(x3_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   const int g_row = lane >> 3, g_slot = lane & 7;
 
   const int nchunks = (p.cin_pad + XBK - 1) / XBK;
@@ -123,7 +106,7 @@ __global__ __launch_bounds__(256, MF == 2 ? 3 : 2) void tdnn_gemm_x3_kernel(cons
     const int grp = min(wn + i * 4, XGROUPS - 1);
     const int w = grp * 8 + g_row;
     const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-    a_off[i] = (size_t)row * x_pitch + (size_t)xswz(w, g_slot) * 16u;
+    a_off[i] = (size_t)row * x_pitch + (size_t)lds_swz(w, g_slot) * 16u;
   }
   auto issue_A = [&](int c, int st) {
     const unsigned char *base = xg + (size_t)c * XROWB;
@@ -133,8 +116,8 @@ __global__ __launch_bounds__(256, MF == 2 ? 3 : 2) void tdnn_gemm_x3_kernel(cons
       const int grp = min(wn + i * 4, XGROUPS - 1);
       const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + st * XSTAGE + grp * 1024);
       const int w = grp * 8 + g_row;
-      const bool ok = !tail || (c * XBK + xswz(w, g_slot) * 4 < p.cin_pad);
-      x3_glds16(ok ? base + a_off[i] : zero, dst);
+      const bool ok = !tail || (c * XBK + lds_swz(w, g_slot) * 4 < p.cin_pad);
+      glds16(ok ? base + a_off[i] : zero, dst);
     }
   };
 
@@ -165,11 +148,11 @@ __global__ __launch_bounds__(256, MF == 2 ? 3 : 2) void tdnn_gemm_x3_kernel(cons
       const int item = it * 256 + tid;
       if (item < Geo::WIN * 4) {
         const int w = item >> 2, q = item & 3;
-        const uint4 a = *reinterpret_cast<const uint4 *>(src + w * XROWB + xswz(w, 2 * q) * 16);
-        const uint4 b = *reinterpret_cast<const uint4 *>(src + w * XROWB + xswz(w, 2 * q + 1) * 16);
+        const uint4 a = *reinterpret_cast<const uint4 *>(src + w * XROWB + lds_swz(w, 2 * q) * 16);
+        const uint4 b = *reinterpret_cast<const uint4 *>(src + w * XROWB + lds_swz(w, 2 * q + 1) * 16);
         const X3Frag f = x3_split<ET, true>(a, b, range);
-        *reinterpret_cast<uint4 *>(dst + w * XROWB + xswz(w, q) * 16) = f.hi;
-        *reinterpret_cast<uint4 *>(dst + w * XROWB + xswz(w, 4 + q) * 16) = f.lo;
+        *reinterpret_cast<uint4 *>(dst + w * XROWB + lds_swz(w, q) * 16) = f.hi;
+        *reinterpret_cast<uint4 *>(dst + w * XROWB + lds_swz(w, 4 + q) * 16) = f.lo;
       }
     }
   };
@@ -180,8 +163,8 @@ __global__ __launch_bounds__(256, MF == 2 ? 3 : 2) void tdnn_gemm_x3_kernel(cons
 #pragma unroll
       for (int i = 0; i < MF; ++i) {
         const int w = i * 32 + lr + kHalo + d;
-        x.f[i].hi = *reinterpret_cast<const uint4 *>(Ib + w * XROWB + xswz(w, sh) * 16);
-        x.f[i].lo = *reinterpret_cast<const uint4 *>(Ib + w * XROWB + xswz(w, 4 + sh) * 16);
+        x.f[i].hi = *reinterpret_cast<const uint4 *>(Ib + w * XROWB + lds_swz(w, sh) * 16);
+        x.f[i].lo = *reinterpret_cast<const uint4 *>(Ib + w * XROWB + lds_swz(w, 4 + sh) * 16);
       }
       return;
     }
@@ -190,8 +173,8 @@ __global__ __launch_bounds__(256, MF == 2 ? 3 : 2) void tdnn_gemm_x3_kernel(cons
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
       const int w = i * 32 + lr + kHalo + d;
-      const uint4 a = *reinterpret_cast<const uint4 *>(Ab + w * XROWB + xswz(w, s0) * 16);
-      const uint4 b = *reinterpret_cast<const uint4 *>(Ab + w * XROWB + xswz(w, s0 + 1) * 16);
+      const uint4 a = *reinterpret_cast<const uint4 *>(Ab + w * XROWB + lds_swz(w, s0) * 16);
+      const uint4 b = *reinterpret_cast<const uint4 *>(Ab + w * XROWB + lds_swz(w, s0 + 1) * 16);
       x.f[i] = x3_split<ET, (TERMS & 2) != 0>(a, b, range);
     }
   };

@@ -18,7 +18,7 @@
 // Plain and generic epilogues of kernels_tdnn_x3.hip; the fused-pooling and 64-row forms stay on the three-product kernel.
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -36,39 +36,6 @@ constexpr int QRING = 4 * QSTAGE;              // two f32 stages + two images
 static_assert(4 * 32 * QSPITCH * 4 <= QRING, "epilogue scratch must fit in the ring");
 static_assert(QBN == kBigTileN, "weight padding must match the N tile");
 
-constexpr int kQScaleWhi = 127 + 6, kQScaleWlo = 127 - 6, kQScaleXlo = 127 - 11, kQScaleXhi = 127;     // kernels_tdnn_chainm.hip
-
-typedef __attribute__((address_space(3))) unsigned char x3m_lds_byte;
-typedef int q_v8i __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ int qswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void x3m_glds16(const void *gsrc, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-__device__ __forceinline__ uint32_t q_range_bits(uint32_t packed_hi) { return (packed_hi & 0x7fff7fffu) + 0x05000500u; }      // |half| >= 57344
-
-template <bool SEL>
-__device__ __forceinline__ void q_split(float v0, float v1, uint32_t &hi16, int &hi8, int &lo8, uint32_t &range) {
-  hi16 = pack_h16x2<ET_F16>(v0, v1);
-  range |= q_range_bits(hi16);
-  float r0, r1;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi16), "v"(v0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi16), "v"(v1));
-  hi8 = __builtin_amdgcn_cvt_pk_bf8_f32(v0, v1, hi8, SEL);
-  lo8 = __builtin_amdgcn_cvt_pk_bf8_f32(r0 * 2048.0f, r1 * 2048.0f, lo8, SEL);
-}
-
 // XIMG: the input rows are IMAGES already (p.x_image: written by this kernel's image epilogue, p.y_image, in the producing layer - see the
 // epilogue): the window of a chunk goes by LDS-DMA straight into one of FOUR image slots (ring), no conversion pass, no f32 stage.
 template <bool GENERIC, bool XIMG>
@@ -77,7 +44,7 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
   const int tid = threadIdx.x, lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 31, lh = lane >> 5;
-  const int scale_w = lh ? kQScaleWlo : kQScaleWhi, scale_x = lh ? kQScaleXhi : kQScaleXlo;
+  const int scale_w = lh ? kScaleWlo : kScaleWhi, scale_x = lh ? kScaleXhi : kScaleXlo;
 
   const int tile = xcd_swizzle(blockIdx.x, m_tiles * n_tiles);
   const int m0 = (tile / n_tiles) * QBM;
@@ -86,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
   const unsigned char *xg = reinterpret_cast<const unsigned char *>(p.x);
   const unsigned char *zero = reinterpret_cast<const unsigned char *>(p.zero16);
   const size_t x_pitch = (size_t)p.ldx * 4;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(x3m_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   const int g_row = lane >> 3, g_slot = lane & 7;
 
   const int nchunks = (p.cin_pad + QBK - 1) / QBK;
@@ -110,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
     const int grp = min(wn + i * 4, QGROUPS - 1);
     const int w = grp * 8 + g_row;
     const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-    a_off[i] = (size_t)row * x_pitch + (size_t)qswz(w, g_slot) * 16u;
+    a_off[i] = (size_t)row * x_pitch + (size_t)lds_swz(w, g_slot) * 16u;
   }
   auto issue_A = [&](int c) {
     const unsigned char *base = xg + (size_t)c * QROWB;
@@ -120,8 +87,8 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
       const int grp = min(wn + i * 4, QGROUPS - 1);
       const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + (XIMG ? (c & 3) : (c & 1)) * QSTAGE + grp * 1024);
       const int w = grp * 8 + g_row;
-      const bool ok = !tail || (c * QBK + qswz(w, g_slot) * 4 < p.cin_pad);
-      x3m_glds16(ok ? base + a_off[i] : zero, dst);
+      const bool ok = !tail || (c * QBK + lds_swz(w, g_slot) * 4 < p.cin_pad);
+      glds16(ok ? base + a_off[i] : zero, dst);
     }
   };
   uint32_t range = 0u;
@@ -135,18 +102,18 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
       const int item = it * 256 + tid;
       if (item < QWIN * 4) {
         const int w = item >> 2, q = item & 3;
-        const uint4 a = *reinterpret_cast<const uint4 *>(src + w * QROWB + qswz(w, 2 * q) * 16);
-        const uint4 b = *reinterpret_cast<const uint4 *>(src + w * QROWB + qswz(w, 2 * q + 1) * 16);
+        const uint4 a = *reinterpret_cast<const uint4 *>(src + w * QROWB + lds_swz(w, 2 * q) * 16);
+        const uint4 b = *reinterpret_cast<const uint4 *>(src + w * QROWB + lds_swz(w, 2 * q + 1) * 16);
         uint4 hi;
         int h8a = 0, l8a = 0, h8b = 0, l8b = 0;
-        q_split<false>(__uint_as_float(a.x), __uint_as_float(a.y), hi.x, h8a, l8a, range);
-        q_split<true>(__uint_as_float(a.z), __uint_as_float(a.w), hi.y, h8a, l8a, range);
-        q_split<false>(__uint_as_float(b.x), __uint_as_float(b.y), hi.z, h8b, l8b, range);
-        q_split<true>(__uint_as_float(b.z), __uint_as_float(b.w), hi.w, h8b, l8b, range);
-        *reinterpret_cast<uint4 *>(dst + w * QROWB + qswz(w, q) * 16) = hi;
+        split_mx<false>(__uint_as_float(a.x), __uint_as_float(a.y), hi.x, h8a, l8a, range);
+        split_mx<true>(__uint_as_float(a.z), __uint_as_float(a.w), hi.y, h8a, l8a, range);
+        split_mx<false>(__uint_as_float(b.x), __uint_as_float(b.y), hi.z, h8b, l8b, range);
+        split_mx<true>(__uint_as_float(b.z), __uint_as_float(b.w), hi.w, h8b, l8b, range);
+        *reinterpret_cast<uint4 *>(dst + w * QROWB + lds_swz(w, q) * 16) = hi;
         // byte b of an 8-bit slot of lane half lh = channel (b < 8 ? 8 lh + b : 16 + 8 lh + b - 8): the order of the lane's two half fragments
-        *reinterpret_cast<uint2 *>(dst + w * QROWB + qswz(w, 4 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)l8a, (uint32_t)l8b);
-        *reinterpret_cast<uint2 *>(dst + w * QROWB + qswz(w, 6 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)h8a, (uint32_t)h8b);
+        *reinterpret_cast<uint2 *>(dst + w * QROWB + lds_swz(w, 4 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)l8a, (uint32_t)l8b);
+        *reinterpret_cast<uint2 *>(dst + w * QROWB + lds_swz(w, 6 + (q & 1)) * 16 + (q >> 1) * 8) = make_uint2((uint32_t)h8a, (uint32_t)h8b);
       }
     }
   };
@@ -187,8 +154,8 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
   };
   // corrections of accumulator (i, j): x0 / x1 = the frame fragment's K blocks 0 (x_lo8) / 1 (x_hi8)
   auto mma_mx = [&](int i, int j, const uint4 &x0, const uint4 &x1) {
-    const q_v8i a = {(int)wq[j].x, (int)wq[j].y, (int)wq[j].z, (int)wq[j].w, (int)we[j].x, (int)we[j].y, (int)we[j].z, (int)we[j].w};
-    const q_v8i b = {(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
+    const v8i a = {(int)wq[j].x, (int)wq[j].y, (int)wq[j].z, (int)wq[j].w, (int)we[j].x, (int)we[j].y, (int)we[j].z, (int)we[j].w};
+    const v8i b = {(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
     acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc[i][j], 0, 1, 0, scale_w, 0, scale_x);      // e4m3 weights, e5m2 activations
   };
 
@@ -349,8 +316,8 @@ __global__ __launch_bounds__(256, 2) void tdnn_gemm_x3m_kernel(const TdnnKernelP
           // pass would write them - the reader's results are bit-identical to those from the f32 row
           uint2 hi;
           int h8 = 0, l8 = 0;
-          q_split<false>(y[0], y[1], hi.x, h8, l8, range);
-          q_split<true>(y[2], y[3], hi.y, h8, l8, range);
+          split_mx<false>(y[0], y[1], hi.x, h8, l8, range);
+          split_mx<true>(y[2], y[3], hi.y, h8, l8, range);
           unsigned char *rowb = reinterpret_cast<unsigned char *>(scr + lr * QSPITCH) + j * 128;
           *reinterpret_cast<uint2 *>(rowb + q * 16 + lh * 8) = hi;
           *reinterpret_cast<uint32_t *>(rowb + 64 + (q & 1) * 16 + (q >> 1) * 8 + lh * 4) = (uint32_t)l8;

@@ -40,7 +40,8 @@
 #include <cstdlib>
 #include <utility>
 
-#include "device_utils.h"
+#include "chain_pool.h"
+#include "lds_dma.h"
 
 namespace asv {
 namespace {
@@ -63,25 +64,9 @@ constexpr int CHAIN4_LDS = 163840;
 constexpr int kMaxLastWidth = (CHAIN4_LDS - LAST_OFF) / 8;   // 2816 output channels
 static_assert(CSTAGES * CSTAGE <= Y_BYTES, "the window ring lives inside the Y region");
 
-typedef __attribute__((address_space(3))) unsigned char chain_lds_byte;
 template <int V> struct IC { static constexpr int value = V; };
 template <int... Is, class F> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F &&f) { (f(IC<Is>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
-
-__device__ __forceinline__ int cswz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ void chain_glds16_s(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 
 // The accumulators are the wave's 256 AGPRs, managed BY HAND: tile T (0..15) = a[16 T .. 16 T + 15], every matrix instruction, every
 // read and every write of them is inline assembly naming the registers.  (Left to hipcc, the two alternating accumulator sets of
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(256, 1) void tdnn_chain4_kernel(const TdnnChainPara
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // 0..3: 128-channel slice of the 512-wide layers
   const int lr = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * CM;
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(chain_lds_byte *)lds);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   float *par = reinterpret_cast<float *>(lds + SCR_OFF);
   const uint32_t lane16 = (uint32_t)lane * 16u;
 
@@ -193,10 +178,7 @@ __global__ __launch_bounds__(256, 1) void tdnn_chain4_kernel(const TdnnChainPara
     *reinterpret_cast<float4 *>(last_scale + k) = p.last.scale != nullptr ? *reinterpret_cast<const float4 *>(p.last.scale + k) : make_float4(1.f, 1.f, 1.f, 1.f);
   }
   // the last layer's view of the tile's rows, fetched here, behind the first window's latency
-  int first_seg = -1;
-#pragma unroll
-  for (int k = 0; k < kHalo + 1; ++k)
-    if (first_seg < 0 && m0 + k < p.rows) first_seg = p.row_seg[m0 + k];
+  const int first_seg = pool_first_seg(p, m0);
   const int rowseg_lo = p.row_seg[m0 + lane], rowseg_hi = p.row_seg[m0 + 64 + lane];
 
   uint4 wf[4][4];
@@ -242,7 +224,7 @@ __global__ __launch_bounds__(256, 1) void tdnn_chain4_kernel(const TdnnChainPara
       const int grp = min(wave + i * NWAVES, CGROUPS - 1);
       const int w = grp * 8 + g_row;
       const int row = min(max(m0 - kHalo + w, 0), p.rows - 1);
-      a_off[i] = (uint32_t)row * (uint32_t)x_pitch + (uint32_t)cswz(w, g_slot) * 16u;
+      a_off[i] = (uint32_t)row * (uint32_t)x_pitch + (uint32_t)lds_swz(w, g_slot) * 16u;
     }
     auto issue_A = [&](int c, int st) {
       const unsigned char *base = xg + (size_t)c * (CBK * 2);
@@ -250,7 +232,7 @@ __global__ __launch_bounds__(256, 1) void tdnn_chain4_kernel(const TdnnChainPara
       for (int i = 0; i < CPIECES; ++i) {
         const int grp = min(wave + i * NWAVES, CGROUPS - 1);
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + st * CSTAGE + grp * 1024);
-        chain_glds16_s(base, a_off[i], dst);
+        glds16_s(base, a_off[i], dst);
       }
     };
     const size_t frag_stride = (size_t)n_taps * nchunks * 4096;
@@ -468,6 +450,7 @@ __global__ __launch_bounds__(256, 1) void tdnn_chain4_kernel(const TdnnChainPara
     const __amdgpu_buffer_rsrc_t pres = wfrag_rsrc(p.pool_partial + (size_t)half * p.pool_slots * 6 * p.ld_partial);
     const uint32_t pvoff = (uint32_t)(lh * 3 * p.ld_partial + lr) * 4u;
     const uint32_t pld = (uint32_t)p.ld_partial * 4u;
+    // (the buffer-store twin of chain_pool.h pool_publish_moments: the same slot rule, layout and scaling - change both together)
     auto publish = [&]() {
       const int slot = cur_seg - first_seg;
       if constexpr (ABL == 7) { asm volatile("" ::"v"(ps[0]), "v"(ps[1]), "v"(pq[0]), "v"(pq[1]), "v"(pv[0]), "v"(pv[1])); return; }   // ablation: no stores

@@ -14,17 +14,26 @@ CSRC = os.path.join(REPO, "asv-subtools_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
+def device_asm(unit, out, dev=False):
+    """Device assembly of one translation unit at `out`, compiled with exactly the flags the Makefile builds its object with (`make
+    print-flags`; dev: the developer build's); returns hipcc's kernel-resource-usage remarks."""
+    flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags", "UNIT=" + unit] + (["DEV=1"] if dev else []), capture_output=True, text=True)
+    assert flags.returncode == 0, flags.stderr[-2000:]
+    src = unit + ".hip" if os.path.exists(os.path.join(CSRC, unit + ".hip")) else os.path.join("tools", unit + ".hip")
+    r = subprocess.run([HIPCC] + flags.stdout.split() + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out), src],
+                       cwd=CSRC, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stderr
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
 def test_chain4_kernel_has_no_spills_and_no_compiler_owned_agprs(tmp_path):
     out = tmp_path / "chain4.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-Xclang", "-target-feature", "-Xclang",
-           "-packed-fp32-ops", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out), "-DASV_WITH_ABLATION", os.path.join(CSRC, "tools", "kernels_tdnn_chain4.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels = re.findall(r"Function Name: (\S+)", r.stderr)
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", r.stderr)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    agprs = [int(x) for x in re.findall(r"AGPRs: (\d+)", r.stderr)]
+    remarks = device_asm("kernels_tdnn_chain4", out, dev=True)
+    kernels = re.findall(r"Function Name: (\S+)", remarks)
+    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", remarks)]
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", remarks)]
+    agprs = [int(x) for x in re.findall(r"AGPRs: (\d+)", remarks)]
     assert len(kernels) >= 2 and len(spills) == len(kernels)
     assert all(s == 0 for s in spills) and all(s == 0 for s in scratch), (spills, scratch)
     assert all(a == 256 for a in agprs), agprs                   # the kernel descriptor covers the whole accumulator file
@@ -52,11 +61,7 @@ def test_persistent_f32x_convolution_kernels_keep_their_weights_in_registers(tmp
     kernels inside 256 registers WITHOUT spilling into scratch (a spilled fragment would be re-read from memory inside the K loop)
     and the LDS rings leave room for two workgroups (the 64-row / 8-wave form: one)."""
     out = tmp_path / "x3.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-Xclang", "-target-feature", "-Xclang",
-           "-packed-fp32-ops", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out), os.path.join(CSRC, "kernels_conv2d_x3.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
+    blocks = re.split(r"remark: [^\n]*Function Name: ", device_asm("kernels_conv2d_x3", out))[1:]
     seen = 0
     for b in blocks:
         name = b.split()[0]
@@ -73,19 +78,15 @@ def test_persistent_f32x_convolution_kernels_keep_their_weights_in_registers(tmp
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-@pytest.mark.parametrize("src,extra", [("kernels_tdnn_p8.hip", []), ("kernels_tdnn_p8x.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])])
-def test_8phase_kernels_have_no_spills_and_no_compiler_visible_vector_loads(tmp_path, src, extra):
+@pytest.mark.parametrize("src", ["kernels_tdnn_p8.hip", "kernels_tdnn_p8x.hip"])
+def test_8phase_kernels_have_no_spills_and_no_compiler_visible_vector_loads(tmp_path, src):
     """The 8-phase kernels (kernels_tdnn_p8.hip, kernels_tdnn_p8x.hip) issue every vector-memory read as LDS-DMA from inline assembly
     and wait with counted `s_waitcnt vmcnt(N)`: hipcc counts only the vector-memory operations it knows of, so ONE load of its own in
     the tile loop - or one spilled register (scratch is vector memory) - turns into waits that, in hardware terms, drain the DMA pieces
     in flight (the first p8x build spilled 30 registers across the K loop and got a `vmcnt(0)` at the top of every tile).  Build-time
     check: no spills, no scratch, 2 waves per SIMD, and no global / scratch / buffer load instruction of the compiler's behind a kernel's first DMA."""
     out = tmp_path / "k.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-Wno-inline-asm"] + extra + [
-        "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out), os.path.join(CSRC, src)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
+    blocks = re.split(r"remark: [^\n]*Function Name: ", device_asm(src[:-len(".hip")], out))[1:]
     assert len(blocks) >= 4
     for b in blocks:
         name = b.split()[0]
@@ -122,10 +123,7 @@ def test_res2_chain_kernel_forms_fit_their_lds_and_registers(tmp_path):
     them (the first FR = 7 build spilled the 7 DMA source addresses of a lane: scratch reloads between the window pieces).  The images
     B and X share one buffer: 111 104 / 127 488 bytes of LDS (an array of registers in the streaming step was once promoted to LDS by
     hipcc: + 32 KiB, silently)."""
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-c",
-                        "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "res2.o"), os.path.join(CSRC, "kernels_res2.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
+    blocks = re.split(r"remark: [^\n]*Function Name: ", device_asm("kernels_res2", tmp_path / "res2.s"))[1:]
     assert len(blocks) == 4
     for b in blocks:
         name = b.split()[0]
@@ -146,11 +144,7 @@ def test_f32m_kernels_fit_their_registers_and_lds(tmp_path):
     seen = {}
     for name in ("kernels_tdnn_chainm.hip", "kernels_tdnn_x3m.hip"):
         out = tmp_path / (name + ".s")
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(REPO, "include"), "-I" + CSRC, "-Xclang", "-target-feature", "-Xclang",
-               "-packed-fp32-ops", "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(out), os.path.join(CSRC, name)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        for block in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
+        for block in re.split(r"remark: [^\n]*Function Name: ", device_asm(name[:-len(".hip")], out))[1:]:
             fn = block.split()[0]
             seen[fn] = {k: int(re.search(p, block).group(1)) for k, p in (("vgprs", r" VGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
                                                                          ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"))}

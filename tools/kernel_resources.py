@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Developer tool: registers / spills / occupancy / LDS of every kernel of one translation unit, from hipcc's
--Rpass-analysis=kernel-resource-usage (build container; no GPU needed).    tools/kernel_resources.py kernels_tdnn_chain [filter]"""
+-Rpass-analysis=kernel-resource-usage (build container; no GPU needed), compiled with the flags the Makefile builds the unit with
+(`make print-flags`; --dev: the developer build's, implied for units that exist only there).
+    tools/kernel_resources.py [--dev] kernels_tdnn_chain [filter]"""
 import re, subprocess, sys, os
 csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "asv-subtools_amd", "csrc")
-unit = sys.argv[1]
-flt = sys.argv[2] if len(sys.argv) > 2 else ""
-extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] if unit in ("kernels_tdnn_x3", "kernels_tdnn_chainx", "kernels_tdnn_chain4") else []
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(csrc, "..", "..", "include"), "-I" + csrc] + extra + \
-      ["-c", os.path.join(csrc, unit + ".hip") if os.path.exists(os.path.join(csrc, unit + ".hip")) else os.path.join(csrc, "tools", unit + ".hip"),
-       "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + (["-DASV_WITH_ABLATION"] if unit == "kernels_tdnn_chain4" else [])
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+args = [a for a in sys.argv[1:] if a != "--dev"]
+unit = args[0]
+flt = args[1] if len(args) > 1 else ""
+in_tools = not os.path.exists(os.path.join(csrc, unit + ".hip"))
+dev = "--dev" in sys.argv or in_tools
+flags = subprocess.run(["make", "-s", "-C", csrc, "print-flags", "UNIT=" + unit] + (["DEV=1"] if dev else []), capture_output=True, text=True, check=True).stdout.split()
+cmd = ["/opt/rocm/bin/hipcc"] + flags + ["-c", os.path.join("tools", unit + ".hip") if in_tools else unit + ".hip", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
+r = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
+if r.returncode != 0:
+    sys.exit(r.stderr[-4000:])
+out = r.stderr
 cur = None
 rows = {}
 for line in out.splitlines():
