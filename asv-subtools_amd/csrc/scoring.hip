@@ -357,6 +357,233 @@ __global__ __launch_bounds__(256) void score_norm_cross_kernel(const float *ec, 
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------
+// DET curve, minimum detection cost and Cavg (reference kaldi/sid/compute_min_dcf.py:54-106, computeCavg.py:82-117).
+// Everything the reference compares or counts is an integer here; every float64 expression the reference evaluates is evaluated
+// with the same operations in the same order, without contraction: the results are the reference's bit for bit.
+namespace {
+
+constexpr int kDcfMaxPoints = 8;
+constexpr int kDcfMaxBlocks = 1024;
+constexpr int kCavgLdsBins = 4096;         // per-wave LDS histogram up to this many counters (4 waves x 16 KiB); beyond: global atomics
+
+// key = order-preserving image of the score in the high word, TRIAL INDEX in the low word: an ascending sort is Python's stable
+// sorted(enumerate(scores), key=itemgetter(1)) (compute_min_dcf.py:59-61) - ties keep the input order, whatever their labels.
+// -0.0 == +0.0 in Python but not in the bit image: both become +0.0 in the key.
+__global__ __launch_bounds__(256) void det_keys_kernel(const float *scores, int n, unsigned long long *keys, int *nan_flag) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)n) return;
+  const float x = scores[i];
+  if (x != x) atomicOr(nan_flag, 1);
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  keys[i] = ((unsigned long long)u << 32) | (unsigned long long)i;
+}
+// labels and the scores themselves (a -0.0 stays -0.0) in sorted order
+__global__ __launch_bounds__(256) void det_gather_kernel(const unsigned long long *sorted, const float *scores, const int32_t *labels, int n, int *lab, float *thr) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)n) return;
+  const unsigned src = (unsigned)(sorted[i] & 0xffffffffull);
+  lab[i] = labels[src] != 0;
+  thr[i] = scores[src];
+}
+// compute_min_dcf.py:83,88 - int / float(norm), 1 - int / float(norm)
+__device__ __forceinline__ void det_rates(int cum_tgt, unsigned i, int num_p, int num_n, double &fnr, double &fpr) {
+#pragma clang fp contract(off)
+  fnr = (double)cum_tgt / (double)num_p;
+  fpr = 1.0 - (double)((int)(i + 1u) - cum_tgt) / (double)num_n;
+}
+__global__ __launch_bounds__(256) void det_rates_kernel(const int *cum_tgt, int n, int num_p, int num_n, double *fnr, double *fpr) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)n) return;
+  double a, b;
+  det_rates(cum_tgt[i], i, num_p, num_n, a, b);
+  fnr[i] = a;
+  fpr[i] = b;
+}
+
+struct DcfPoints { int n; double c_miss[kDcfMaxPoints], p_target[kDcfMaxPoints], c_fa[kDcfMaxPoints], p_non[kDcfMaxPoints]; };
+
+// compute_min_dcf.py:99, ((c_miss * fnr) * p_target) + ((c_fa * fpr) * (1 - p_target)): five roundings, no fused multiply-add
+__device__ __forceinline__ double dcf_cost(double c_miss, double fnr, double p_target, double c_fa, double fpr, double p_non) {
+#pragma clang fp contract(off)
+  const double miss = c_miss * fnr * p_target;
+  const double fa = c_fa * fpr * p_non;
+  return miss + fa;
+}
+// the reference's `if c_det < min_c_det` over ascending i keeps the FIRST minimum: (cost, index) ordered lexicographically
+__device__ __forceinline__ void dcf_take(double &c, int &i, double oc, int oi) {
+  if (oc < c || (oc == c && oi < i)) { c = oc; i = oi; }
+}
+__device__ __forceinline__ void dcf_block_min(double &c, int &i, double *sh_c, int *sh_i) {       // sh_*: 4 entries; result valid in thread 0
+  for (int o = 32; o > 0; o >>= 1) dcf_take(c, i, __shfl_xor(c, o), __shfl_xor(i, o));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sh_c[threadIdx.x >> 6] = c; sh_i[threadIdx.x >> 6] = i; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < 4; ++w) dcf_take(c, i, sh_c[w], sh_i[w]);
+}
+// one pass over the sorted trials for all operating points: per thread, then wavefront, then workgroup; blk_*[point][block]
+__global__ __launch_bounds__(256) void dcf_sweep_kernel(const int *cum_tgt, int n, int num_p, int num_n, DcfPoints pts, double *blk_cost, int *blk_idx) {
+  __shared__ double sh_c[4];
+  __shared__ int sh_i[4];
+  double best[kDcfMaxPoints];
+  int at[kDcfMaxPoints];
+#pragma unroll
+  for (int p = 0; p < kDcfMaxPoints; ++p) { best[p] = __builtin_inf(); at[p] = 0x7fffffff; }
+  const unsigned stride = gridDim.x * 256u;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)n; i += stride) {
+    double fnr, fpr;
+    det_rates(cum_tgt[i], i, num_p, num_n, fnr, fpr);
+#pragma unroll
+    for (int p = 0; p < kDcfMaxPoints; ++p)
+      if (p < pts.n) {
+        const double c = dcf_cost(pts.c_miss[p], fnr, pts.p_target[p], pts.c_fa[p], fpr, pts.p_non[p]);
+        if (c < best[p]) { best[p] = c; at[p] = (int)i; }
+      }
+  }
+#pragma unroll
+  for (int p = 0; p < kDcfMaxPoints; ++p)
+    if (p < pts.n) {
+      double c = best[p];
+      int i = at[p];
+      dcf_block_min(c, i, sh_c, sh_i);
+      if (threadIdx.x == 0) { blk_cost[p * gridDim.x + blockIdx.x] = c; blk_idx[p * gridDim.x + blockIdx.x] = i; }
+    }
+}
+// last stage: one workgroup per operating point over the per-workgroup minima
+__global__ __launch_bounds__(256) void dcf_final_kernel(const double *blk_cost, const int *blk_idx, int n_blocks, const float *thr, double *cost, float *thr_at) {
+  __shared__ double sh_c[4];
+  __shared__ int sh_i[4];
+  const int p = blockIdx.x;
+  double c = __builtin_inf();
+  int i = 0x7fffffff;
+  for (int b = threadIdx.x; b < n_blocks; b += 256) dcf_take(c, i, blk_cost[p * n_blocks + b], blk_idx[p * n_blocks + b]);
+  dcf_block_min(c, i, sh_c, sh_i);
+  if (threadIdx.x == 0) {
+    cost[p] = c;
+    thr_at[p] = thr[i == 0x7fffffff ? 0 : i];                   // no finite cost anywhere: min_c_det stays inf at thresholds[0]
+  }
+}
+
+// Sort by (score, trial index), gather, scan.  On return cum[i] = targets among the i + 1 lowest scores, thr[i] = the i-th lowest
+// score (device; `thr` may be the caller's buffer or nullptr for workspace), `extra` further workspace bytes sit at *extra_ptr.
+int det_prepare(const char *who, const float *scores, const int32_t *labels, int n, float *thr, size_t extra, Workspace &g_ws, int **cum_out, float **thr_out,
+                void **extra_ptr, int *num_p, hipStream_t s) {
+  size_t sort_tmp = 0, scan_tmp = 0;
+  ASV_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr, n, 0, 64, s));
+  ASV_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_tmp, (int *)nullptr, (int *)nullptr, n, s));
+  const size_t tmp = round_up64((int64_t)std::max(sort_tmp, scan_tmp), 256);
+  const size_t n8 = round_up64((int64_t)n * 8, 256), n4 = round_up64((int64_t)n * 4, 256);
+  void *ws = nullptr;
+  int rc = g_ws.get(2 * n8 + 3 * n4 + 256 + tmp + extra, s, &ws);
+  if (rc) return rc;
+  unsigned char *b = reinterpret_cast<unsigned char *>(ws);
+  unsigned long long *keys = reinterpret_cast<unsigned long long *>(b), *sorted = reinterpret_cast<unsigned long long *>(b + n8);
+  int *lab = reinterpret_cast<int *>(b + 2 * n8), *cum = reinterpret_cast<int *>(b + 2 * n8 + n4);
+  if (!thr) thr = reinterpret_cast<float *>(b + 2 * n8 + 2 * n4);
+  int *nan_flag = reinterpret_cast<int *>(b + 2 * n8 + 3 * n4);
+  void *cub_tmp = b + 2 * n8 + 3 * n4 + 256;
+  *extra_ptr = b + 2 * n8 + 3 * n4 + 256 + tmp;
+  const dim3 grid(((unsigned)n + 255u) / 256u), block(256);
+  ASV_HIP_CHECK(hipMemsetAsync(nan_flag, 0, 4, s));
+  hipLaunchKernelGGL(det_keys_kernel, grid, block, 0, s, scores, n, keys, nan_flag);
+  size_t t1 = tmp;
+  ASV_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(cub_tmp, t1, keys, sorted, n, 0, 64, s));
+  hipLaunchKernelGGL(det_gather_kernel, grid, block, 0, s, sorted, scores, labels, n, lab, thr);
+  size_t t2 = tmp;
+  ASV_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(cub_tmp, t2, lab, cum, n, s));
+  int has_nan = 0;
+  ASV_HIP_CHECK(hipMemcpyAsync(num_p, cum + (n - 1), 4, hipMemcpyDeviceToHost, s));
+  ASV_HIP_CHECK(hipMemcpyAsync(&has_nan, nan_flag, 4, hipMemcpyDeviceToHost, s));
+  ASV_HIP_CHECK(hipStreamSynchronize(s));
+  ASV_REQUIRE(!has_nan, "%s: NaN among the scores (a NaN has no place in a sorted list)", who);
+  ASV_REQUIRE(*num_p > 0 && n - *num_p > 0, "%s: need both target and non-target trials (%d / %d)", who, *num_p, n - *num_p);
+  *cum_out = cum;
+  *thr_out = thr;
+  return ASV_OK;
+}
+
+// one pass: score range (as order-preserving keys; stats[0] = max of ~key, stats[1] = max of key, so that zero initialises both)
+// and the validity of every id; stats[2]: bit 0 NaN score, bit 1 model_lang outside [0, lang_num), bit 2 true_lang outside [-1, lang_num)
+__global__ __launch_bounds__(256) void cavg_range_kernel(const float *scores, const int32_t *model_lang, const int32_t *true_lang, int n, int lang_num, uint32_t *stats) {
+  uint32_t lo = 0, hi = 0, bad = 0;
+  const unsigned stride = gridDim.x * 256u;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)n; i += stride) {
+    const float x = scores[i];
+    const int m = model_lang[i], t = true_lang[i];
+    if (x != x) bad |= 1u;
+    if (m < 0 || m >= lang_num) bad |= 2u;
+    if (t < -1 || t >= lang_num) bad |= 4u;
+    uint32_t u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    const uint32_t k = score_key(__uint_as_float(u));
+    lo = max(lo, ~k);
+    hi = max(hi, k);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = max(lo, (uint32_t)__shfl_xor((int)lo, o));
+    hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
+    bad |= (uint32_t)__shfl_xor((int)bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(&stats[0], lo);
+    atomicMax(&stats[1], hi);
+    if (bad) atomicOr(&stats[2], bad);
+  }
+}
+// hist[model][true (lang_num = unknown)][k], k = how many of the bins + 1 thresholds are <= the score (compared in float64 like the
+// reference: `score < threshold` misses, `score >= threshold` accepts).  The thresholds ascend (a product and a sum of non-negative
+// terms, rounded monotonically), so k comes from a binary search and threshold s accepts exactly the pairs with k > s.
+__global__ __launch_bounds__(256) void cavg_hist_kernel(const float *scores, const int32_t *model_lang, const int32_t *true_lang, int n, int lang_num, int bins,
+                                                        const double *thr, uint32_t *hist, int per_wave_lds) {
+  extern __shared__ uint32_t lds_hist[];
+  const int H = lang_num * (lang_num + 1) * (bins + 2);
+  uint32_t *mine = lds_hist + (size_t)(threadIdx.x >> 6) * H;
+  if (per_wave_lds) {
+    for (int j = threadIdx.x; j < 4 * H; j += 256) lds_hist[j] = 0u;
+    __syncthreads();
+  }
+  const unsigned stride = gridDim.x * 256u;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)n; i += stride) {
+    const double x = (double)scores[i];
+    int lo = 0, hi = bins + 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (thr[mid] <= x) lo = mid + 1; else hi = mid;
+    }
+    const int t = true_lang[i];
+    const int slot = (model_lang[i] * (lang_num + 1) + (t < 0 ? lang_num : t)) * (bins + 2) + lo;
+    if (per_wave_lds) atomicAdd(&mine[slot], 1u); else atomicAdd(&hist[slot], 1u);
+  }
+  if (per_wave_lds) {
+    __syncthreads();
+    for (int j = threadIdx.x & 63; j < H; j += 64) {
+      const uint32_t v = mine[j];
+      if (v) atomicAdd(&hist[j], v);
+    }
+  }
+}
+// in place, per (model, true) row: hist[k] <- pairs with at least k thresholds at or below their score.  Entry 0 is the row's
+// total (LTa / LNa), entry s + 1 the pairs threshold s accepts (LNf; LTm = total - accepted).
+__global__ __launch_bounds__(256) void cavg_suffix_kernel(uint32_t *hist, int rows, int bins) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  uint32_t *h = hist + (size_t)r * (bins + 2);
+  uint32_t acc = 0;
+  for (int k = bins + 1; k >= 0; --k) { acc += h[k]; h[k] = acc; }
+}
+
+float key32_to_score(uint32_t k) {
+  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+}  // namespace
+
 extern "C" {
 
 int asv_mean_vec(const float *x, int n, int dim, float *mean, void *stream) {
@@ -517,4 +744,134 @@ int asv_score_norm(const float *enroll_cohort, int n_enroll, const float *test_c
   return ASV_OK;
 }
 
+int asv_det_curve(const float *scores, const int32_t *labels, int n, double *fnr, double *fpr, float *thresholds, void *stream) {
+  ASV_REQUIRE(scores && labels && fnr && fpr && thresholds && n >= 2, "asv_det_curve: bad argument (n = %d, at least 2 trials)", n);
+  ASV_ENTER(scores);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Workspace g_ws;
+  int *cum = nullptr, num_p = 0;
+  float *thr = nullptr;
+  void *extra = nullptr;
+  int rc = det_prepare("asv_det_curve", scores, labels, n, thresholds, 0, g_ws, &cum, &thr, &extra, &num_p, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(det_rates_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, s, cum, n, num_p, n - num_p, fnr, fpr);
+  ASV_HIP_CHECK(hipGetLastError());
+  return ASV_OK;
+}
+
+int asv_min_dcf(const float *scores, const int32_t *labels, int n, const double *p_target, const double *c_miss, const double *c_fa, int n_points,
+                double *min_dcf, float *threshold, void *stream) {
+  ASV_REQUIRE(scores && labels && p_target && c_miss && c_fa && min_dcf && threshold, "asv_min_dcf: bad argument");
+  ASV_REQUIRE(n >= 2, "asv_min_dcf: %d trial(s), at least 2 needed", n);
+  ASV_REQUIRE(n_points >= 1 && n_points <= kDcfMaxPoints, "asv_min_dcf: %d operating points, 1 .. %d per call", n_points, kDcfMaxPoints);
+  DcfPoints pts;
+  memset(&pts, 0, sizeof(pts));
+  pts.n = n_points;
+  for (int p = 0; p < n_points; ++p) {
+    ASV_REQUIRE(c_fa[p] > 0, "asv_min_dcf: c_fa must be greater than 0 (point %d: %g)", p, c_fa[p]);
+    ASV_REQUIRE(c_miss[p] > 0, "asv_min_dcf: c_miss must be greater than 0 (point %d: %g)", p, c_miss[p]);
+    ASV_REQUIRE(p_target[p] > 0 && p_target[p] < 1, "asv_min_dcf: p_target must be greater than 0 and less than 1 (point %d: %g)", p, p_target[p]);
+    pts.c_miss[p] = c_miss[p]; pts.p_target[p] = p_target[p]; pts.c_fa[p] = c_fa[p]; pts.p_non[p] = 1 - p_target[p];
+  }
+  ASV_ENTER(scores);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int n_blocks = (int)std::min<int64_t>(((int64_t)n + 255) / 256, kDcfMaxBlocks);
+  const size_t part8 = round_up64((int64_t)kDcfMaxPoints * n_blocks * 8, 256), part4 = round_up64((int64_t)kDcfMaxPoints * n_blocks * 4, 256);
+  Workspace g_ws;
+  int *cum = nullptr, num_p = 0;
+  float *thr = nullptr;
+  void *extra = nullptr;
+  int rc = det_prepare("asv_min_dcf", scores, labels, n, nullptr, part8 + part4 + 512, g_ws, &cum, &thr, &extra, &num_p, s);
+  if (rc) return rc;
+  unsigned char *b = reinterpret_cast<unsigned char *>(extra);
+  double *blk_cost = reinterpret_cast<double *>(b), *cost = reinterpret_cast<double *>(b + part8 + part4);
+  int *blk_idx = reinterpret_cast<int *>(b + part8);
+  float *thr_at = reinterpret_cast<float *>(b + part8 + part4 + 256);
+  hipLaunchKernelGGL(dcf_sweep_kernel, dim3(n_blocks), dim3(256), 0, s, cum, n, num_p, n - num_p, pts, blk_cost, blk_idx);
+  hipLaunchKernelGGL(dcf_final_kernel, dim3(n_points), dim3(256), 0, s, blk_cost, blk_idx, n_blocks, thr, cost, thr_at);
+  ASV_HIP_CHECK(hipGetLastError());
+  double h_cost[kDcfMaxPoints];
+  ASV_HIP_CHECK(hipMemcpyAsync(h_cost, cost, 8 * n_points, hipMemcpyDeviceToHost, s));
+  ASV_HIP_CHECK(hipMemcpyAsync(threshold, thr_at, 4 * n_points, hipMemcpyDeviceToHost, s));
+  ASV_HIP_CHECK(hipStreamSynchronize(s));
+  for (int p = 0; p < n_points; ++p) {
+    // compute_min_dcf.py:104-105
+    const double a = pts.c_miss[p] * pts.p_target[p], f = pts.c_fa[p] * pts.p_non[p];
+    min_dcf[p] = h_cost[p] / (f < a ? f : a);
+  }
+  return ASV_OK;
+}
+
+int asv_cavg(const float *scores, const int32_t *model_lang, const int32_t *true_lang, int n, int lang_num, int bins, double p_target, double *cavgs,
+             double *min_cavg, void *stream) {
+#pragma clang fp contract(off)
+  ASV_REQUIRE(scores && model_lang && true_lang && cavgs && min_cavg && n >= 1, "asv_cavg: bad argument");
+  ASV_REQUIRE(lang_num >= 2, "asv_cavg: %d language(s), at least 2 needed (the non-target prior is (1 - p_target) / (lang_num - 1))", lang_num);
+  ASV_REQUIRE(bins >= 1, "asv_cavg: %d threshold bins, at least 1 needed", bins);
+  const int64_t H = (int64_t)lang_num * (lang_num + 1) * (bins + 2);
+  ASV_REQUIRE(H <= (1ll << 26), "asv_cavg: %d languages x %d bins need %lld counters, more than this call keeps", lang_num, bins, (long long)H);
+  ASV_ENTER(scores);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t thr_bytes = round_up64((int64_t)(bins + 1) * 8, 256), hist_bytes = round_up64(H * 4, 256);
+  Workspace g_ws;
+  void *ws = nullptr;
+  int rc = g_ws.get(256 + thr_bytes + hist_bytes, s, &ws);
+  if (rc) return rc;
+  unsigned char *b = reinterpret_cast<unsigned char *>(ws);
+  uint32_t *stats = reinterpret_cast<uint32_t *>(b), *hist = reinterpret_cast<uint32_t *>(b + 256 + thr_bytes);
+  double *thr = reinterpret_cast<double *>(b + 256);
+  const int n_blocks = (int)std::min<int64_t>(((int64_t)n + 255) / 256, 1024);
+  ASV_HIP_CHECK(hipMemsetAsync(stats, 0, 256, s));
+  ASV_HIP_CHECK(hipMemsetAsync(hist, 0, hist_bytes, s));
+  hipLaunchKernelGGL(cavg_range_kernel, dim3(n_blocks), dim3(256), 0, s, scores, model_lang, true_lang, n, lang_num, stats);
+  uint32_t h_stats[3] = {0, 0, 0};
+  ASV_HIP_CHECK(hipMemcpyAsync(h_stats, stats, 12, hipMemcpyDeviceToHost, s));
+  ASV_HIP_CHECK(hipStreamSynchronize(s));
+  ASV_REQUIRE(!(h_stats[2] & 1u), "asv_cavg: NaN among the scores");
+  ASV_REQUIRE(!(h_stats[2] & 2u), "asv_cavg: model_lang outside [0, %d)", lang_num);
+  ASV_REQUIRE(!(h_stats[2] & 4u), "asv_cavg: true_lang outside [-1, %d) (-1 = unknown)", lang_num);
+  const double min_score = (double)key32_to_score(~h_stats[0]), max_score = (double)key32_to_score(h_stats[1]);
+  ASV_REQUIRE(max_score != min_score, "asv_cavg: all %d scores equal %g - the reference divides by the zero range (max - min) / bins of its thresholds", n, min_score);
+  // computeCavg.py:86-88
+  std::vector<double> h_thr(bins + 1);
+  const double precision = (max_score - min_score) / bins;
+  for (int section = 0; section <= bins; ++section) h_thr[section] = min_score + section * precision;
+  ASV_HIP_CHECK(hipMemcpyAsync(thr, h_thr.data(), 8 * (size_t)(bins + 1), hipMemcpyHostToDevice, s));
+  const int per_wave_lds = H <= kCavgLdsBins;
+  hipLaunchKernelGGL(cavg_hist_kernel, dim3(n_blocks), dim3(256), per_wave_lds ? (size_t)H * 16 : 0, s, scores, model_lang, true_lang, n, lang_num, bins, thr, hist,
+                     per_wave_lds);
+  const int rows = lang_num * (lang_num + 1);
+  hipLaunchKernelGGL(cavg_suffix_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, hist, rows, bins);
+  ASV_HIP_CHECK(hipGetLastError());
+  std::vector<uint32_t> h(H);
+  ASV_HIP_CHECK(hipMemcpyAsync(h.data(), hist, (size_t)H * 4, hipMemcpyDeviceToHost, s));
+  ASV_HIP_CHECK(hipStreamSynchronize(s));
+  // computeCavg.py:89-117 on the counts.  at(m, c, k): pairs of model m and true language c (lang_num: unknown) that at least k
+  // thresholds accept.  The reference files an unknown utterance (-1) under LNa[-1] / LNf[-1]: the LAST language's slot, for every
+  // model language - also for the last one itself, whose own slot is otherwise empty.  It is never a target.
+  auto at = [&](int m, int c, int k) { return h[((size_t)m * (lang_num + 1) + c) * (bins + 2) + k]; };
+  const double p_nontarget = (1 - p_target) / (lang_num - 1);
+  double best = 0.0;
+  for (int section = 0; section <= bins; ++section) {
+    double total = 0.0;
+    for (int lang = 0; lang < lang_num; ++lang) {
+      const double LTa = (double)at(lang, lang, 0), LTm = (double)(at(lang, lang, 0) - at(lang, lang, section + 1));
+      double p_miss = 0.0, sum_fa = 0.0;
+      if (LTa != 0.0) p_miss = LTm / LTa;
+      for (int i = 0; i < lang_num; ++i) {
+        uint64_t na = i == lang ? 0 : at(lang, i, 0), nf = i == lang ? 0 : at(lang, i, section + 1);
+        if (i == lang_num - 1) { na += at(lang, lang_num, 0); nf += at(lang, lang_num, section + 1); }
+        double p_fa = 0.0;
+        if (na != 0) p_fa = (double)nf / (double)na;
+        sum_fa = sum_fa + p_fa;
+      }
+      const double miss_term = p_target * p_miss, fa_term = p_nontarget * sum_fa;
+      total = total + (miss_term + fa_term);
+    }
+    cavgs[section] = total / lang_num;
+    if (section == 0 || cavgs[section] < best) best = cavgs[section];
+  }
+  *min_cavg = best;
+  return ASV_OK;
+}
 }  // extern "C"

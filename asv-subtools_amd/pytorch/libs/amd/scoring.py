@@ -6,6 +6,7 @@ Replaces the process chain the reference runs per scoring job (bash -> Kaldi bin
     score/process.sh:156-203   ivector-mean, ivector-subtract-global-mean, ivector-normalize-length
     score/score.sh:82-121      ivector-compute-dot-products, ivector-plda-scoring
     computeEER.sh / computeEER-like-Bosaris.py:50-91
+    kaldi/sid/compute_min_dcf.py:54-106 (det_curve, min_dcf), computeCavg.py:82-117 (cavg)
 and the numpy PLDA of score/pyplda/plda_base.py: statistics + EM training (asv_plda_train, float64 on the device -
 SURVEY.md 8(f) rank 4) and scoring; only the final D x D diagonalisation (Cholesky + eigh) is host numpy.
 
@@ -166,6 +167,71 @@ def eer(scores, labels):
     e, thr = C.c_float(0), C.c_float(0)
     capi.check(capi.lib().asv_eer(_ptr(s), _ptr(l), s.shape[0], C.byref(e), C.byref(thr), _stream(s)), "asv_eer")
     return float(e.value), float(thr.value)
+
+
+def det_curve(scores, labels):
+    """ComputeErrorRates of kaldi/sid/compute_min_dcf.py:54-89 on the device: (fnr float64 [n], fpr float64 [n], thresholds
+    float32 [n]) device tensors over the trials sorted by score, ties in input order."""
+    import torch
+    s = _dev(scores, torch.float32)
+    l = _dev(labels, torch.int32, s.device)
+    if s.dim() != 1 or l.shape != s.shape:
+        raise ValueError("det_curve: %s scores but %s labels" % (tuple(s.shape), tuple(l.shape)))
+    n = s.shape[0]
+    fnr = torch.empty(n, dtype=torch.float64, device=s.device)
+    fpr = torch.empty(n, dtype=torch.float64, device=s.device)
+    thr = torch.empty(n, dtype=torch.float32, device=s.device)
+    capi.check(capi.lib().asv_det_curve(_ptr(s), _ptr(l), n, _ptr(fnr), _ptr(fpr), _ptr(thr), _stream(s)), "asv_det_curve")
+    return fnr, fpr, thr
+
+
+MIN_DCF_POINTS_PER_CALL = 8
+
+
+def min_dcf(scores, labels, p_target=0.01, c_miss=1, c_fa=1):
+    """Minimum normalised detection cost and its threshold (compute_min_dcf.py:93-106).  Each of p_target / c_miss / c_fa is a
+    scalar or a sequence; sequences must agree in length and give lists of results, one per operating point - up to 8 points
+    share one sort and one sweep on the device, longer lists run in groups of 8.  All scalars: (min_dcf, threshold) floats."""
+    import torch
+    args = (p_target, c_miss, c_fa)
+    seq = [not np.isscalar(a) for a in args]
+    lengths = {len(a) for a, q in zip(args, seq) if q}
+    if len(lengths) > 1:
+        raise ValueError("min_dcf: p_target / c_miss / c_fa sequences of different lengths %s" % sorted(lengths))
+    n_points = lengths.pop() if lengths else 1
+    if n_points == 0:
+        return [], []
+    pt, cm, cf = (np.ascontiguousarray(a, dtype=np.float64) if q else np.full(n_points, float(a)) for a, q in zip(args, seq))
+    s = _dev(scores, torch.float32)
+    l = _dev(labels, torch.int32, s.device)
+    if s.dim() != 1 or l.shape != s.shape:
+        raise ValueError("min_dcf: %s scores but %s labels" % (tuple(s.shape), tuple(l.shape)))
+    dcf, thr = np.zeros(n_points, dtype=np.float64), np.zeros(n_points, dtype=np.float32)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    for b in range(0, n_points, MIN_DCF_POINTS_PER_CALL):
+        e = min(n_points, b + MIN_DCF_POINTS_PER_CALL)
+        capi.check(capi.lib().asv_min_dcf(_ptr(s), _ptr(l), s.shape[0], dp(pt[b:e]), dp(cm[b:e]), dp(cf[b:e]), e - b, dp(dcf[b:e]), capi.f32_ptr(thr[b:e]),
+                                          _stream(s)), "asv_min_dcf")
+    if any(seq):
+        return [float(x) for x in dcf], [float(x) for x in thr]
+    return float(dcf[0]), float(thr[0])
+
+
+def cavg(scores, model_lang, true_lang, lang_num, bins=20, p_target=0.5):
+    """Language-recognition average cost (computeCavg.py:82-117): scores [n] of (model language, utterance) pairs, model_lang
+    [n] in [0, lang_num), true_lang [n] the utterance's language or -1 when unknown.  Returns (min_cavg, cavgs): the minimum
+    over the bins + 1 thresholds between the lowest and the highest score, and the value at each of them (floats)."""
+    import torch
+    s = _dev(scores, torch.float32)
+    m, t = _dev(model_lang, torch.int32, s.device), _dev(true_lang, torch.int32, s.device)
+    if s.dim() != 1 or m.shape != s.shape or t.shape != s.shape:
+        raise ValueError("cavg: %s scores, %s model_lang, %s true_lang" % (tuple(s.shape), tuple(m.shape), tuple(t.shape)))
+    bins = int(bins)
+    out = np.zeros(max(bins, 0) + 1, dtype=np.float64)
+    best = C.c_double(0.0)
+    capi.check(capi.lib().asv_cavg(_ptr(s), _ptr(m), _ptr(t), s.shape[0], int(lang_num), bins, float(p_target),
+                                   out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(best), _stream(s)), "asv_cavg")
+    return float(best.value), [float(x) for x in out]
 
 
 def score_normalize(scores, enroll_cohort, test_cohort, enroll_idx, test_idx, top_n=300, cross_select=False):

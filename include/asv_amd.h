@@ -19,7 +19,7 @@
  *   asv_tdnn_forward    <- TdnnAffine.forward + _BaseActivationBatchNorm.forward
  *                          (libs/nnet/components.py:107-149, 418-431) on one layer.
  *   asv_stats_pool_forward <- StatisticsPooling.forward (libs/nnet/pooling.py:32-69).
- *   asv_cosine_* / asv_length_norm / asv_plda_* / asv_eer: see the scoring section below.
+ *   asv_cosine_* / asv_length_norm / asv_plda_* / asv_eer / asv_det_curve / asv_min_dcf / asv_cavg: see the scoring section below.
  *
  * Data layout: activations are "frames x channels" row-major (the Kaldi matrix layout,
  * libs/support/kaldi_io.py:466-496), utterances packed back to back; `offsets[n_utts+1]`
@@ -407,6 +407,27 @@ int asv_eer(const float *scores, const int32_t *labels, int n, float *eer_percen
 int asv_score_norm(const float *enroll_cohort, int n_enroll, const float *test_cohort, int n_test, int n_cohort,
                    const int32_t *ei, const int32_t *ti, const float *scores, int n_trials, int top_n,
                    int cross_select, float *normed, void *stream);
+/* DET curve (kaldi/sid/compute_min_dcf.py:54-89, ComputeErrorRates) of device scores with device int32 labels (non-zero =
+ * target).  The trials are sorted by score alone, ties in input order (-0.0 and +0.0 tie); a NaN score is an error.
+ * fnr[i] = targets among the i + 1 lowest scores / all targets, fpr[i] = 1 - non-targets among them / all non-targets (float64,
+ * these very operations), thresholds[i] = the i-th lowest score: device outputs of n elements each.  Synchronises `stream`. */
+int asv_det_curve(const float *scores, const int32_t *labels, int n, double *fnr, double *fpr, float *thresholds,
+                  void *stream);
+/* Minimum normalised detection cost (compute_min_dcf.py:93-106, ComputeMinDcf) at n_points (1 .. 8) operating points from ONE
+ * sort and one sweep: c_det = c_miss * fnr * p_target + c_fa * fpr * (1 - p_target) in float64 in that order, unfused; the
+ * first minimum over the sorted trials; divided by min(c_miss * p_target, c_fa * (1 - p_target)).  p_target / c_miss / c_fa /
+ * min_dcf / threshold are host arrays of n_points elements.  Errors: n < 2, a class without trials, c_* <= 0, p_target outside
+ * (0, 1), NaN scores.  Synchronises `stream`. */
+int asv_min_dcf(const float *scores, const int32_t *labels, int n, const double *p_target, const double *c_miss,
+                const double *c_fa, int n_points, double *min_dcf, float *threshold, void *stream);
+/* Language-recognition average cost (computeCavg.py:82-117, get_cavg) of n device (model language, utterance) pairs:
+ * model_lang in [0, lang_num), true_lang in [0, lang_num) or -1 for an utterance of unknown language, which - like the
+ * reference's LNa[-1] - counts as a non-target of the last language for every model language.  The bins + 1 thresholds
+ * min + section * ((max - min) / bins) are float64; the pairs are counted on the device, the float64 arithmetic on the counts
+ * runs on the host in the reference's order.  cavgs (host, bins + 1 values), min_cavg (host).  Errors: lang_num < 2, bins < 1,
+ * ids out of range, NaN scores, all scores equal.  Synchronises `stream`. */
+int asv_cavg(const float *scores, const int32_t *model_lang, const int32_t *true_lang, int n, int lang_num, int bins,
+             double p_target, double *cavgs, double *min_cavg, void *stream);
 
 /* ---- PLDA training --------------------------------------------------
  * Statistics + EM of score/pyplda/plda_base.py:37-81, 227-300 in float64 on the device.  x: device f32 [n_rows][ldx]
