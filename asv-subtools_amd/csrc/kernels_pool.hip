@@ -201,7 +201,8 @@ __global__ __launch_bounds__(256) void stats_pool_kernel(const PoolKernelParams 
       if (p.stddev) {
         // sum (x-mean)^2 = sum (x-c)^2 - n (mean-c)^2
         const float var = fmaxf(q[i] - n * dmean * dmean, 0.0f) / counts;
-        const float sd = (p.var_mode == ASV_POOL_VAR_ADD) ? sqrtf(var + p.eps) : sqrtf(fmaxf(var, p.eps));
+        // (var < eps ? eps : var, not fmaxf: a NaN variance - unbiased == 2 at one frame - stays NaN, as torch.clamp leaves it)
+        const float sd = (p.var_mode == ASV_POOL_VAR_ADD) ? sqrtf(var + p.eps) : sqrtf(var < p.eps ? p.eps : var);
         p.out[(size_t)seg * p.ld_out + ocol + p.channels + ch + i] = sd;
       }
     }
@@ -320,7 +321,7 @@ __global__ __launch_bounds__(64) void pool_finish_kernel(const PoolFinishParams 
   p.out[(size_t)seg * p.ld_out + ch] = mean + (p.shift ? p.shift[ch] : 0.0f);
   if (p.stddev) {
     const float var = m2 / counts;
-    p.out[(size_t)seg * p.ld_out + p.channels + ch] = (p.var_mode == ASV_POOL_VAR_ADD) ? sqrtf(var + p.eps) : sqrtf(fmaxf(var, p.eps));
+    p.out[(size_t)seg * p.ld_out + p.channels + ch] = (p.var_mode == ASV_POOL_VAR_ADD) ? sqrtf(var + p.eps) : sqrtf(var < p.eps ? p.eps : var);   // NaN stays NaN (stats_pool_kernel)
   }
 }
 
