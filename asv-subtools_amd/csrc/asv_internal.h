@@ -162,7 +162,7 @@ bool grid_conv_narrow_supported(const TdnnKernelParams &p, int et);
 size_t grid_conv_frag_elems(int cin_pad, int cout_pad32, int n_taps = 9);
 bool grid_conv_s2d_supported(const TdnnKernelParams &p, int et);      // 128 (4 phases x 32) -> 64 channels, 4 backward taps
 int launch_grid_conv_s2d(const TdnnKernelParams &p, hipStream_t s);
-int launch_grid_conv_narrow(const TdnnKernelParams &p, hipStream_t s);
+int launch_grid_conv_narrow(const TdnnKernelParams &p, hipStream_t s, bool *persistent = nullptr);      // *persistent: which of its two kernels ran
 bool grid_conv_wide_supported(const TdnnKernelParams &p, int et);      // the C = 128 / 256 stages (same fragment order)
 int launch_grid_conv_wide(const TdnnKernelParams &p, hipStream_t s);
 bool grid_conv_c1_supported(const TdnnKernelParams &p, int et, int in_ch);

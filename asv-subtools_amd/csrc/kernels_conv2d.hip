@@ -737,7 +737,7 @@ bool grid_conv_narrow_supported(const TdnnKernelParams &p, int et) {
 // elements of the fragment-ordered weight copy for this kernel
 size_t grid_conv_frag_elems(int cin_pad, int cout_pad32, int n_taps) { return (size_t)n_taps * (cin_pad / 16) * (cout_pad32 / 32) * 512; }
 
-int launch_grid_conv_narrow(const TdnnKernelParams &p0, hipStream_t s) {
+int launch_grid_conv_narrow(const TdnnKernelParams &p0, hipStream_t s, bool *persistent) {
   TdnnKernelParams p = p0;
   static const bool live = getenv("ASV_AMD_LIVE_TUNE") != nullptr;
   p.tune = 0;
@@ -745,6 +745,7 @@ int launch_grid_conv_narrow(const TdnnKernelParams &p0, hipStream_t s) {
   p.tune = live && getenv("ASV_AMD_CONV_ABL") != nullptr ? atoi(getenv("ASV_AMD_CONV_ABL")) : 0;
 #endif
   ASV_REQUIRE(grid_conv_narrow_supported(p, true), "grid conv (narrow): unsupported layer");
+  if (persistent != nullptr) *persistent = false;
   const dim3 grid(p.rows / CBM), block(256);
   const bool fast = (p.act1 == ASV_ACT_NONE || p.act1 == ASV_ACT_RELU) && p.act2 == ASV_ACT_NONE && !p.affine_first && p.seg_bias == nullptr &&
                     p.seg_scale == nullptr && p.res == nullptr;
@@ -755,13 +756,17 @@ int launch_grid_conv_narrow(const TdnnKernelParams &p0, hipStream_t s) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const int bm = p.cin_pad == 32 ? NarrowPers<32>::BM : NarrowPers<64>::BM, per_cu = 2;
-    const int n_tiles = p.rows / bm, wgs = std::min(n_tiles, cus * per_cu), per_wg = (n_tiles + wgs - 1) / wgs;
+    // developer aid (ASV_AMD_CONV_PERS_WGS=n with ASV_AMD_LIVE_TUNE=1; same results): at most n workgroups, so that a short batch walks
+    // many tiles per workgroup and the ring wraps (tests/test_gpu_grid_conv_h16.py)
+    const int cap = live && getenv("ASV_AMD_CONV_PERS_WGS") != nullptr ? atoi(getenv("ASV_AMD_CONV_PERS_WGS")) : 0;
+    const int n_tiles = p.rows / bm, wgs = std::min(n_tiles, cap > 0 ? std::min(cap, cus * per_cu) : cus * per_cu), per_wg = (n_tiles + wgs - 1) / wgs;
     const dim3 pgrid((n_tiles + per_wg - 1) / per_wg);
 #define ASV_CONV_PERS(...) do { if (p.et == ET_F16) hipLaunchKernelGGL((__VA_ARGS__, ET_F16>), pgrid, block, 0, s, p, per_wg); \
                                 else hipLaunchKernelGGL((__VA_ARGS__, ET_BF16>), pgrid, block, 0, s, p, per_wg); } while (0)
     if (p.cin_pad == 32) { if (fast) ASV_CONV_PERS(grid_conv_narrow_pers_kernel<32, false); else ASV_CONV_PERS(grid_conv_narrow_pers_kernel<32, true); }
     else { if (fast) ASV_CONV_PERS(grid_conv_narrow_pers_kernel<64, false); else ASV_CONV_PERS(grid_conv_narrow_pers_kernel<64, true); }
 #undef ASV_CONV_PERS
+    if (persistent != nullptr) *persistent = true;
     ASV_HIP_CHECK(hipGetLastError());
     return ASV_OK;
   }

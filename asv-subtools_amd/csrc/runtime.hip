@@ -260,7 +260,7 @@ struct asv_net {
 
 namespace {
 
-std::atomic<unsigned long long> g_kernel_launches[8];       // asv_kernel_launch_count
+std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_CONV_S2D + 1];       // asv_kernel_launch_count (ids start at 1)
 
 // the range-status word of the f32x kernels lives behind the zero page's zeros (own 64-byte line; kernels only ever OR into it)
 uint32_t *status_word(asv_net *net) { return reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(net->zero_page) + 128); }
@@ -1066,7 +1066,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream) {
 }
 
 unsigned long long asv_kernel_launch_count(int which) {
-  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_MQ_ATTPOOL) ? g_kernel_launches[which].load() : 0ull;
+  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_CONV_S2D) ? g_kernel_launches[which].load() : 0ull;
 }
 
 size_t asv_net_device_bytes(const asv_net_t *net) {
@@ -1674,10 +1674,15 @@ int run_ops(RunCtx &c, size_t n_ops) {
             // the bf16 split here would be the largest error left in the f32x mode (< 0.3 % of the FLOPs: +1 % of an f32x step)
             rc = launch_utts_gemm(p, bp.segments, net->frames_h16(), c.s);
             break;
-          case TdnnPath::ConvNarrow: rc = launch_grid_conv_narrow(p, c.s); break;
-          case TdnnPath::ConvWide: rc = launch_grid_conv_wide(p, c.s); break;
-          case TdnnPath::ConvS2d: rc = launch_grid_conv_s2d(p, c.s); break;
-          case TdnnPath::ConvC1: rc = launch_grid_conv_c1(p, c.s); break;
+          case TdnnPath::ConvNarrow: {
+            bool persistent = false;
+            rc = launch_grid_conv_narrow(p, c.s, &persistent);
+            ++g_kernel_launches[persistent ? ASV_KERNEL_CONV_NARROW_PERS : ASV_KERNEL_CONV_NARROW];
+            break;
+          }
+          case TdnnPath::ConvWide: rc = launch_grid_conv_wide(p, c.s); ++g_kernel_launches[ASV_KERNEL_CONV_WIDE]; break;
+          case TdnnPath::ConvS2d: rc = launch_grid_conv_s2d(p, c.s); ++g_kernel_launches[ASV_KERNEL_CONV_S2D]; break;
+          case TdnnPath::ConvC1: rc = launch_grid_conv_c1(p, c.s); ++g_kernel_launches[ASV_KERNEL_CONV_C1]; break;
           case TdnnPath::X3m: rc = launch_tdnn_x3m(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_X3M]; break;
           case TdnnPath::P8x: rc = launch_tdnn_p8x(p, c.s); ++g_kernel_launches[ASV_KERNEL_TDNN_P8X]; break;
           case TdnnPath::X3: rc = launch_tdnn_x3(p, c.s); break;

@@ -22,6 +22,7 @@ PLDA_NORM_NONE, PLDA_NORM_SIMPLE, PLDA_NORM_PSI = 0, 1, 2
 STATUS_HALF_RANGE = 1
 KERNEL_TDNN_P8, KERNEL_TDNN_BIG3, KERNEL_TDNN_P8X, KERNEL_TDNN_CHAINM, KERNEL_TDNN_X3M, KERNEL_TDNN_X3M_IMAGE = 1, 2, 3, 4, 5, 6
 KERNEL_MQ_ATTPOOL = 7
+KERNEL_CONV_C1, KERNEL_CONV_NARROW, KERNEL_CONV_NARROW_PERS, KERNEL_CONV_WIDE, KERNEL_CONV_S2D = 8, 9, 10, 11, 12
 
 ACT_BY_NAME = {None: ACT_NONE, "": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}

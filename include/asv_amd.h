@@ -316,6 +316,11 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream);
 #define ASV_KERNEL_TDNN_X3M 5    /* kernels_tdnn_x3m.hip: the f32x wide-layer kernel in the same form */
 #define ASV_KERNEL_TDNN_X3M_IMAGE 6 /* launches of that kernel that wrote their output rows as images for an f32m reader (counted in 5 as well) */
 #define ASV_KERNEL_MQ_ATTPOOL 7   /* kernels_pool.hip: mq_attentive_pool_kernel, the one-launch multi-query multi-head attentive pooling */
+#define ASV_KERNEL_CONV_C1 8      /* kernels_conv2d.hip: grid_conv_c1_kernel, the one-input-channel first convolution of the 2-D trunk */
+#define ASV_KERNEL_CONV_NARROW 9  /* grid_conv_narrow_kernel: C = 32 / 64, one tile per workgroup */
+#define ASV_KERNEL_CONV_NARROW_PERS 10 /* grid_conv_narrow_pers_kernel: the same layers as a persistent sliding-window kernel */
+#define ASV_KERNEL_CONV_WIDE 11   /* grid_conv_wide_kernel: C = 128 / 256 */
+#define ASV_KERNEL_CONV_S2D 12    /* grid_conv_s2d_kernel: the 128 -> 64 space-to-depth form of the stride-2 convolution */
 unsigned long long asv_kernel_launch_count(int which);
 
 /* Bytes of device memory currently held by the net (weights + activation arena). */
