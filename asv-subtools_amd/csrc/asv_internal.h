@@ -254,6 +254,17 @@ struct Res2KernelParams {
   int et;                       // ET_BF16 / ET_F16
 };
 int launch_res2_chain(const Res2KernelParams &p, hipStream_t s);
+// the 64-channel-wide Res2 chain with any one group passing through (kernels_res2n.hip)
+constexpr int kRes2nWidth = 64;
+struct Res2nKernelParams {
+  const void *x; void *y; int ldx, ldy, rows;       // 16-bit rows; x / y already offset to their channel views of (branches + 1) * 64 channels
+  const void *wfrag;                                 // [branches][2 n-frag][3 taps][4 k-groups][lane][8], fragment order of pack_tdnn_weight_frags
+  const float *bias, *scale, *shift;                 // [branches][64]; bias may be nullptr
+  const uint32_t *row_valid;
+  int branches, pass_group, dilation;
+  int et;                                            // ET_BF16 / ET_F16
+};
+int launch_res2n_chain(const Res2nKernelParams &p, hipStream_t s);
 void pack_tdnn_weight_frags(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps,
                             int cout_pad, int cin_pad, uint16_t *dst, uint16_t *dst_lo = nullptr, int et = ET_BF16, float scale = 1.0f);
 // f32-grade split-bf16 kernel of the f32x precision mode (kernels_tdnn_x3.hip): f32 activations, hi / lo weight fragments

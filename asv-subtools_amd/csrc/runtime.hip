@@ -156,7 +156,7 @@ struct Domain {
   int gap() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : pitch + 2; }
 };
 
-enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9 };
+enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10 };
 
 struct Op {
   OpKind kind;
@@ -170,6 +170,7 @@ struct Op {
   asv_grid_flatten_desc_t flat;
   asv_lde_desc_t lde;            // mu / beta live in `scale` / `shift` on the device
   asv_mq_attpool_desc_t mq;
+  asv_res2n_desc_t res2n;        // likewise (bias stays nullptr when the op has none)
   asv_res2_desc_t res2;          // fragments in `wfrag`, per-branch constants in bias / scale / shift
   // device parameters
   void *w = nullptr;
@@ -202,8 +203,8 @@ struct DevMem {
   size_t cap = 0;
 };
 
-const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm"};
-enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_COUNT };   // K_UTTS: affine layers of the pooled domain
+const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain"};
+enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
 
 }  // namespace
 }  // namespace asv
@@ -260,7 +261,7 @@ struct asv_net {
 
 namespace {
 
-std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_CONV_S2D + 1];       // asv_kernel_launch_count (ids start at 1)
+std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_RES2N + 1];       // asv_kernel_launch_count (ids start at 1)
 
 // the range-status word of the f32x kernels lives behind the zero page's zeros (own 64-byte line; kernels only ever OR into it)
 uint32_t *status_word(asv_net *net) { return reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(net->zero_page) + 128); }
@@ -785,6 +786,38 @@ int asv_net_add_res2(asv_net_t *net, const asv_res2_desc_t *d) {
   return ASV_OK;
 }
 
+int asv_net_add_res2n(asv_net_t *net, const asv_res2n_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_res2n: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_res2n_desc_t), "asv_net_add_res2n: struct_size mismatch");
+  ASV_REQUIRE(net->frames_h16(), "res2n: the one-kernel Res2 chain exists for the 16-bit precision modes (bf16, f16) only");
+  ASV_REQUIRE(d->width == kRes2nWidth, "res2n: width %d (the kernel is built for groups of %d channels)", d->width, kRes2nWidth);
+  ASV_REQUIRE(d->groups >= 2 && d->groups <= 8 && d->pass_group >= 0 && d->pass_group < d->groups && d->dilation >= 1 && d->dilation <= kHalo,
+              "res2n: %d groups, pass group %d, dilation %d", d->groups, d->pass_group, d->dilation);
+  ASV_REQUIRE(d->weight && d->scale && d->shift, "res2n: weight / scale / shift are required");
+  const int W = d->width, branches = d->groups - 1, ch = d->groups * W;
+  int rc;
+  if ((rc = check_view(net, d->in_buf, d->in_ch_off, ch, "res2n input"))) return rc;
+  if ((rc = check_view(net, d->out_buf, d->out_ch_off, ch, "res2n output"))) return rc;
+  ASV_REQUIRE(net->bufs[d->in_buf].domain == ASV_DOMAIN_FRAMES && net->bufs[d->out_buf].domain == ASV_DOMAIN_FRAMES && d->out_buf != d->in_buf && d->out_buf != 0,
+              "res2n: frames-domain input and a different frames-domain output buffer");
+  ASV_REQUIRE(d->in_ch_off % 8 == 0 && d->out_ch_off % 8 == 0, "res2n: channel offsets must be multiples of 8 (16-byte row pieces)");
+  Op op; op.kind = OP_RES2N; op.res2n = *d;
+  ASV_ON_DEVICE(net->device);
+  const int tot = 2 * d->dilation + 1;
+  const int taps[3] = {-d->dilation, 0, d->dilation};
+  const size_t per_branch = tdnn_weight_frag_elems(W, W, 3);
+  std::vector<uint16_t> frags(per_branch * branches);
+  for (int b = 0; b < branches; ++b)
+    pack_tdnn_weight_frags(d->weight + (size_t)b * W * W * tot, W, W, tot, -d->dilation, taps, 3, W, W, frags.data() + per_branch * b, nullptr, net->frames_et());
+  if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &op.wfrag))) return rc;
+  if (d->bias != nullptr && (rc = upload_padded(net, d->bias, branches * W, branches * W, 0.0f, &op.bias))) return rc;
+  if ((rc = upload_padded(net, d->scale, branches * W, branches * W, 0.0f, &op.scale))) return rc;
+  if ((rc = upload_padded(net, d->shift, branches * W, branches * W, 0.0f, &op.shift))) return rc;
+  op.res2n.weight = nullptr; op.res2n.bias = nullptr; op.res2n.scale = nullptr; op.res2n.shift = nullptr;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
 int asv_net_add_eltwise(asv_net_t *net, const asv_eltwise_desc_t *d) {
   ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_eltwise: net is null or finalized");
   ASV_REQUIRE(d->struct_size == sizeof(asv_eltwise_desc_t), "asv_net_add_eltwise: struct_size mismatch");
@@ -911,7 +944,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                              o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.x_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.logit_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
-                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
+                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
         for (int rbuf : reads) other_reader |= (rbuf == d.out_buf);
       }
       if (other_reader || d.out_buf == out_buf) continue;
@@ -930,7 +963,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                            o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                            o.kind == OP_ELTWISE ? o.elt.seg_scale_buf : -1, o.kind == OP_ELTWISE ? o.elt.seg_norm_buf : -1, o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
                            o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_IM2COL ? o.i2c.seg_scale_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_GRID_INPUT ? o.gin.in_buf : -1,
-                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
+                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
       for (int rbuf : reads) if (rbuf == buf) return false;
     }
     return true;
@@ -1066,7 +1099,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream) {
 }
 
 unsigned long long asv_kernel_launch_count(int which) {
-  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_CONV_S2D) ? g_kernel_launches[which].load() : 0ull;
+  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_RES2N) ? g_kernel_launches[which].load() : 0ull;
 }
 
 size_t asv_net_device_bytes(const asv_net_t *net) {
@@ -1122,6 +1155,10 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
       case OP_RES2:
         snprintf(line, sizeof(line), "  op %zu: res2 %d[%d] -> %d[%d] branches=%d dilation=%d\n", i, op.res2.in_buf, op.res2.in_ch_off, op.res2.out_buf, op.res2.out_ch_off,
                  op.res2.branches, op.res2.dilation);
+        break;
+      case OP_RES2N:
+        snprintf(line, sizeof(line), "  op %zu: res2n %d[%d] -> %d[%d] width=%d groups=%d pass_group=%d dilation=%d bias=%d\n", i, op.res2n.in_buf, op.res2n.in_ch_off,
+                 op.res2n.out_buf, op.res2n.out_ch_off, op.res2n.width, op.res2n.groups, op.res2n.pass_group, op.res2n.dilation, op.bias != nullptr);
         break;
       case OP_GRID_INPUT:
         snprintf(line, sizeof(line), "  op %zu: grid_input %d -> %d\n", i, op.gin.in_buf, op.gin.out_buf);
@@ -1829,6 +1866,21 @@ int run_ops(RunCtx &c, size_t n_ops) {
           for (int k = 1; k < 14; ++k) fprintf(stderr, " %d:%.0f", k, sum[k] / (double)std::max<size_t>(cnt, 1));
           fprintf(stderr, "\n");
         }
+        break;
+      }
+      case OP_RES2N: {
+        const auto &d = op.res2n;
+        const DomainRun &dr = c.dom[ASV_DOMAIN_FRAMES];
+        Res2nKernelParams p;
+        memset(&p, 0, sizeof(p));
+        p.x = view(c, d.in_buf, d.in_ch_off); p.ldx = net->bufs[d.in_buf].ld;
+        p.y = view(c, d.out_buf, d.out_ch_off); p.ldy = net->bufs[d.out_buf].ld;
+        p.rows = dr.rows_pad; p.wfrag = op.wfrag; p.bias = op.bias; p.scale = op.scale; p.shift = op.shift; p.row_valid = dr.row_valid;
+        p.branches = d.groups - 1; p.pass_group = d.pass_group; p.dilation = d.dilation; p.et = net->frames_et();
+        if ((rc = prof.begin(K_RES2N, 2.0 * (double)bp.frames * d.width * d.width * 3 * (d.groups - 1), (int)i))) return rc;
+        if ((rc = launch_res2n_chain(p, c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_RES2N];
+        if ((rc = prof.end())) return rc;
         break;
       }
       case OP_GRID_INPUT: {

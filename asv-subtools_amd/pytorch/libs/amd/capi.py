@@ -23,6 +23,8 @@ STATUS_HALF_RANGE = 1
 KERNEL_TDNN_P8, KERNEL_TDNN_BIG3, KERNEL_TDNN_P8X, KERNEL_TDNN_CHAINM, KERNEL_TDNN_X3M, KERNEL_TDNN_X3M_IMAGE = 1, 2, 3, 4, 5, 6
 KERNEL_MQ_ATTPOOL = 7
 KERNEL_CONV_C1, KERNEL_CONV_NARROW, KERNEL_CONV_NARROW_PERS, KERNEL_CONV_WIDE, KERNEL_CONV_S2D = 8, 9, 10, 11, 12
+KERNEL_RES2N = 13
+RES2N_TILE_ROWS = 192          # ASV_RES2N_TILE_ROWS: rows a workgroup of res2n_chain_kernel produces
 
 ACT_BY_NAME = {None: ACT_NONE, "": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
@@ -105,6 +107,16 @@ class Res2Desc(C.Structure):
     ]
 
 
+class Res2nDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("in_buf", C.c_int32), ("in_ch_off", C.c_int32),
+        ("out_buf", C.c_int32), ("out_ch_off", C.c_int32),
+        ("width", C.c_int32), ("groups", C.c_int32), ("pass_group", C.c_int32), ("dilation", C.c_int32),
+        ("weight", c_float_p), ("bias", c_float_p), ("scale", c_float_p), ("shift", c_float_p),
+    ]
+
+
 class EltwiseDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -169,7 +181,7 @@ SYMBOLS = [
     "asv_version", "asv_last_error", "asv_device_count",
     "asv_net_create", "asv_net_destroy", "asv_net_define_grid", "asv_net_new_buffer", "asv_net_add_tdnn",
     "asv_net_add_grid_input", "asv_net_add_im2col", "asv_net_add_grid_flatten",
-    "asv_net_add_stats_pool", "asv_net_add_attentive_pool", "asv_net_add_mq_attentive_pool", "asv_net_add_lde_pool", "asv_net_add_eltwise", "asv_net_add_res2",
+    "asv_net_add_stats_pool", "asv_net_add_attentive_pool", "asv_net_add_mq_attentive_pool", "asv_net_add_lde_pool", "asv_net_add_eltwise", "asv_net_add_res2", "asv_net_add_res2n",
     "asv_net_finalize", "asv_net_embed_dim", "asv_net_describe", "asv_net_extract",
     "asv_net_device_bytes", "asv_net_set_profiling", "asv_net_get_profile", "asv_net_status", "asv_net_status_async", "asv_kernel_launch_count",
     "asv_tdnn_forward", "asv_stats_pool_forward",
@@ -220,6 +232,7 @@ def lib():
     L.asv_net_add_lde_pool.argtypes = [vp, C.POINTER(LdeDesc)]
     L.asv_net_add_eltwise.argtypes = [vp, C.POINTER(EltwiseDesc)]
     L.asv_net_add_res2.argtypes = [vp, C.POINTER(Res2Desc)]
+    L.asv_net_add_res2n.argtypes = [vp, C.POINTER(Res2nDesc)]
     L.asv_net_finalize.argtypes = [vp, ci, ci]
     L.asv_net_embed_dim.argtypes = [vp]
     L.asv_net_describe.argtypes = [vp, C.c_char_p, C.c_size_t]

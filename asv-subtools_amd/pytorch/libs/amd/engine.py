@@ -77,6 +77,12 @@ def gather_fuse_on():
     return os.environ.get("ASV_AMD_NO_GATHER_FUSE", "0") in ("0", "", "false")
 
 
+def res2n_on():
+    """ASV_AMD_RES2N=0 keeps the 64-channel-wide Res2 chains (model/ecapa-tdnn-xvector.py) as one layer per branch in the 16-bit modes
+    too (A/B switch; the one-launch form gives the same bits - tests/test_gpu_res2n_kernel.py)."""
+    return os.environ.get("ASV_AMD_RES2N", "1") not in ("0", "false")
+
+
 def mqpool_on():
     """ASV_AMD_MQPOOL=0 keeps the heads x queries attentive poolings of a multi-query multi-head pooling (MQMHASP) as separate
     launches (A/B switch; the one-launch form gives the same bits - tests/test_gpu_mqmha.py)."""
@@ -117,6 +123,8 @@ class Engine(object):
         # 16-bit engines run every Res2NetBlock as one kernel (kernels_res2.hip); the parity modes keep one layer per branch
         fuse = self.precision_base in H16_MODES and (self.flags & (capi.FLAG_REF_KERNELS | capi.FLAG_NO_FUSE | capi.FLAG_SMALL_TILES)) == 0
         ops = g.fused_res2_ops() if fuse else g.ops
+        if fuse and res2n_on():
+            ops = g.fused_res2n_ops(ops)             # the 64-wide chains whose LAST group passes through (kernels_res2n.hip)
         if (self.flags & (capi.FLAG_REF_KERNELS | capi.FLAG_NO_FUSE)) == 0:
             ops = g.fused_add_ops(ops)               # exact in every precision mode (see its docstring)
             if gather_fuse_on():
@@ -144,6 +152,17 @@ class Engine(object):
                 keep = [op.weight, op.bias, op.scale, op.shift]
                 d.weight, d.bias, d.scale, d.shift = (capi.f32_ptr(a) for a in keep)
                 capi.check(L.asv_net_add_res2(self._net, C.byref(d)), "asv_net_add_res2")
+                del keep
+            elif op.kind == "res2n":
+                d = capi.Res2nDesc()
+                d.struct_size = C.sizeof(capi.Res2nDesc)
+                d.in_buf, d.in_ch_off = bv(op.inp)
+                d.out_buf, d.out_ch_off = bv(op.out)
+                d.width, d.groups, d.pass_group, d.dilation = op.width, op.groups, op.pass_group, op.dilation
+                keep = [op.weight, op.bias, op.scale, op.shift]
+                d.weight, d.scale, d.shift = capi.f32_ptr(op.weight), capi.f32_ptr(op.scale), capi.f32_ptr(op.shift)
+                d.bias = capi.f32_ptr(op.bias) if op.bias is not None else None
+                capi.check(L.asv_net_add_res2n(self._net, C.byref(d)), "asv_net_add_res2n")
                 del keep
             elif op.kind == "tdnn":
                 d = capi.TdnnDesc()

@@ -68,7 +68,7 @@ class Op(object):
             names = ("a", "b", "c", "seg_scale", "seg_norm", "d")
         elif self.kind == "im2col":
             names = ("inp", "b", "seg_scale")
-        elif self.kind in ("grid_input", "res2", "flatten"):
+        elif self.kind in ("grid_input", "res2", "res2n", "flatten"):
             names = ("inp",)
         else:
             return list(self.parts)
@@ -77,7 +77,7 @@ class Op(object):
     def input_names(self):
         return {"tdnn": ("inp", "inp2", "seg_bias", "seg_scale", "res"), "pool": ("inp",),
                 "attpool": ("x", "logits"), "mqattpool": ("x", "logits"), "lde": ("x",), "eltwise": ("a", "b", "c", "seg_scale", "seg_norm", "d"), "cat": (), "grid_input": ("inp",),
-                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "flatten": ("inp",)}[self.kind]
+                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",)}[self.kind]
 
 
 class Graph(object):
@@ -256,12 +256,35 @@ class Graph(object):
         self.output = fix(self.output)
 
     def optimize(self):
+        self._fold_relu_bn_into_tdnn()
         self._cse_adds()
         self._fold_eltwise_chains()
         self._fold_adds_into_tdnn()
         self._elide_cats()
         self._drop_dead()
         return self
+
+    def _fold_relu_bn_into_tdnn(self):
+        """bn(F.relu(conv(x))) written with raw torch calls (model/ecapa-tdnn-xvector.py: `self.bn_conv(F.relu(self.conv(out)))`)
+        -> the one fused op a ReluBatchNormTdnnLayer records.  Only the elementwise op sym_relu() recorded is folded, and a
+        BatchNorm only behind such a fold, each when it is the sole reader of a plain affine: programs without F.relu are untouched."""
+        for op in list(self.ops):
+            if op.kind != "eltwise" or op not in self.ops:
+                continue
+            uses, prod = self._use_count(), self._producer()
+            p = prod.get(op.a.tid)
+            whole = op.a.ch_off == 0 and op.a.channels == self.tensors[op.a.tid][1]
+            if p is None or p.kind != "tdnn" or not whole or uses.get(op.a.tid, 0) != 1 or p.act2 is not None or p.seg_scale is not None or p.res is not None:
+                continue
+            bare = all(getattr(op, n, None) is None for n in ("b", "c", "seg_scale", "seg_norm"))
+            if getattr(op, "from_relu", False) and bare and op.scale is None and p.act1 is None and p.scale is None:
+                p.act1, p.relu_folded = "relu", True
+            elif getattr(p, "relu_folded", False) and bare and op.scale is not None and getattr(op, "act", None) is None and p.scale is None:
+                p.scale, p.shift = op.scale, op.shift
+            else:
+                continue
+            self._replace_tensor(op.out.tid, p.out)
+            self.ops.remove(op)
 
     def _is_plain_add(self, op):
         return (op.kind == "eltwise" and op.b is not None and op.c is None and op.seg_scale is None and op.scale is None
@@ -404,6 +427,55 @@ class Graph(object):
             if grp is not None:
                 out.append(grp)
                 i += grp.branches + 1
+            else:
+                out.append(first)
+                i += 1
+        return out
+
+    def fused_res2n_ops(self, ops=None, width=64, max_branches=7, pass_groups=("last",)):
+        """The op list with every Res2 chain over `width`-channel groups whose LAST group passes through (Res2Conv1dReluBn of
+        model/ecapa-tdnn-xvector.py - after cat elision: n dependent TDNN ops, the first y_0 = f(x_0), then y_k = f(y_{k-1} + x_k),
+        writing groups 0 .. n - 1 of one buffer, plus the copy of group n) replaced by ONE 'res2n' op (kernels_res2n.hip).  The
+        bias may be absent - in all branches or in none.  `pass_groups` = ("last", "first") also takes the chains whose FIRST group
+        passes through (what fused_res2_ops matches at width 128): the kernel covers them, the engine does not ask for them -
+        model/ecapa_tdnn_xvector.py at C = 512 keeps its per-branch layers and its bits.  Anything that does
+        not match exactly is left alone; so is everything fused_res2_ops produced."""
+        ops = list(self.ops if ops is None else ops)
+        out, i = [], 0
+        plain = lambda o: (o.kind == "tdnn" and o.act1 == "relu" and o.scale is not None and not o.affine_first and o.act2 is None
+                           and o.seg_bias is None and o.seg_scale is None and o.res is None)
+        copy = lambda o: (o.kind == "eltwise" and all(getattr(o, n, None) is None for n in ("b", "c", "seg_scale", "scale", "act", "seg_norm", "d", "out2")))
+        while i < len(ops):
+            first, grp = ops[i], None
+            if (plain(first) and first.inp2 is None and first.inp.channels == width and first.out.channels == width and len(first.taps) == 3
+                    and first.taps[1] == 0 and first.taps[0] == -first.taps[2] and 1 <= first.taps[2] <= MAX_HALO
+                    and first.inp.ch_off == first.out.ch_off and first.inp.ch_off in (0, width)
+                    and self.domain(first.inp.tid) == DOMAIN_FRAMES and first.inp.tid != first.out.tid):
+                H, O, d = first.inp.tid, first.out.tid, first.taps[2]
+                n = self.tensors[H][1] // width - 1
+                g0 = first.inp.ch_off // width                   # first convolved group: 0 (the last passes) or 1 (the first passes)
+                p = n if g0 == 0 else 0
+                ok = (("last" if g0 == 0 else "first") in pass_groups and self.tensors[H][1] == (n + 1) * width
+                      and self.tensors[O][1] == (n + 1) * width and 1 <= n <= max_branches and i + n < len(ops)
+                      and first.weight.shape == (width, width, 2 * d + 1) and first.w_left == -d)
+                for k in range(1, n):
+                    if not ok:
+                        break
+                    o = ops[i + k]
+                    ok = (plain(o) and o.taps == first.taps and o.inp == View(O, (g0 + k - 1) * width, width) and o.inp2 == View(H, (g0 + k) * width, width)
+                          and o.out == View(O, (g0 + k) * width, width) and o.weight.shape == first.weight.shape and o.w_left == -d
+                          and (o.bias is None) == (first.bias is None))
+                if ok:
+                    cp = ops[i + n]
+                    ok = copy(cp) and cp.a == View(H, p * width, width) and cp.out == View(O, p * width, width)
+                if ok:
+                    br = ops[i:i + n]
+                    stack = lambda name: np.ascontiguousarray(np.stack([getattr(o, name) for o in br]), dtype=np.float32)
+                    grp = Op("res2n", View(O, 0, (n + 1) * width), inp=View(H, 0, (n + 1) * width), width=width, groups=n + 1, pass_group=p, dilation=d,
+                             weight=stack("weight"), bias=None if first.bias is None else stack("bias"), scale=stack("scale"), shift=stack("shift"))
+            if grp is not None:
+                out.append(grp)
+                i += grp.groups
             else:
                 out.append(first)
                 i += 1
@@ -683,7 +755,7 @@ class Sym(object):
         handler = _torch_handlers().get(func)
         if handler is None:
             raise TraceError("torch function %s is not implemented by the MI355X extract path "
-                             "(supported: cat, chunk, add, conv1d(kernel=1), batch_norm(eval), unsqueeze, squeeze)"
+                             "(supported: cat, chunk, add, relu, conv1d(kernel=1), batch_norm(eval), unsqueeze, squeeze)"
                              % getattr(func, "__name__", func))
         return handler(*args, **(kwargs or {}))
 
@@ -750,6 +822,14 @@ def sym_conv1d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
     return Sym(x.graph, x.graph.tdnn(x.view, _np(weight), _np(bias), [0], 0), 3)
 
 
+def sym_relu(x, inplace=False):
+    """F.relu: an elementwise pass, or - behind a plain affine nobody else reads - that affine's activation
+    (Graph._fold_relu_bn_into_tdnn)."""
+    out = x.graph.eltwise(x.view, act="relu")
+    x.graph.ops[-1].from_relu = True
+    return Sym(x.graph, out, x.rank)
+
+
 _HANDLERS = None
 
 
@@ -764,6 +844,7 @@ def _torch_handlers():
             torch.add: lambda a, b, **k: a + b, torch.Tensor.add: lambda a, b, **k: a + b,
             F.batch_norm: sym_batch_norm, torch.batch_norm: sym_batch_norm,
             F.conv1d: sym_conv1d, torch.conv1d: sym_conv1d,
+            F.relu: sym_relu, torch.relu: sym_relu,
             torch.unsqueeze: lambda x, dim: x.unsqueeze(dim), torch.squeeze: lambda x, dim=None: x.squeeze(dim),
         }
     return _HANDLERS
@@ -773,10 +854,80 @@ def _torch_handlers():
 # handlers for modules that model blueprints define themselves (recognised by class name,
 # semantics per /root/reference/pytorch/model/ecapa_tdnn_xvector.py)
 
+def _same_conv_taps(conv, who):
+    """Conv1d(odd kernel, stride 1, "same" padding = dilation * (k - 1) / 2, groups 1) -> (taps, the dense [out, in, right - left + 1]
+    kernel Graph.tdnn takes: the k live taps at their offsets, zeros between)."""
+    k, d = conv.kernel_size[0], conv.dilation[0]
+    h = (k - 1) // 2
+    if (k % 2 != 1 or conv.stride[0] != 1 or conv.groups != 1 or isinstance(conv.padding, str) or conv.padding[0] != d * h
+            or getattr(conv, "padding_mode", "zeros") != "zeros"):
+        raise TraceError("%s: Conv1d(kernel_size=%s, stride=%s, padding=%s, dilation=%s, groups=%s) - supported: an odd kernel, stride 1, "
+                         "padding == dilation * (kernel_size - 1) / 2, groups 1 (taps -h*d .. h*d within +-%d frames)"
+                         % (who, conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, MAX_HALO))
+    w = _np(conv.weight)
+    dense = np.zeros(w.shape[:2] + (2 * h * d + 1,), dtype=np.float32)
+    dense[:, :, ::max(d, 1)] = w
+    return list(range(-h * d, h * d + 1, d)) if h else [0], dense, -h * d
+
+
+def _bn_fold(bn):
+    return fold_batchnorm(_np(bn.running_mean), _np(bn.running_var), _np(bn.weight) if bn.affine else None, _np(bn.bias) if bn.affine else None, bn.eps)
+
+
+def _handle_conv1d_relu_bn(mod, x):
+    """Conv1dReluBn (ecapa-tdnn-xvector.py:60-67): Conv1d -> ReLU -> BatchNorm1d as one fused TDNN op."""
+    taps, w, left = _same_conv_taps(mod.conv, "Conv1dReluBn")
+    scale, shift = _bn_fold(mod.bn)
+    return Sym(x.graph, x.graph.tdnn(x.view, w, _np(mod.conv.bias), taps, left, act1="relu", scale=scale, shift=shift), 3)
+
+
+def _handle_res2_conv1d_relu_bn(mod, x):
+    """Res2Conv1dReluBn (ecapa-tdnn-xvector.py:20-54): `scale` channel groups; the first scale - 1 run through
+    y_i = BN(ReLU(conv_i(y_{i-1} + x_i))) (y_0 = BN(ReLU(conv_0(x_0)))), the LAST passes through."""
+    if x.view.channels != mod.width * mod.scale:
+        raise TraceError("Res2Conv1dReluBn expects %d channels, got %d" % (mod.width * mod.scale, x.view.channels))
+    g = x.graph
+    spx = sym_chunk(x, mod.scale, 1) if mod.scale > 1 else (x,)
+    outs, sp = [], None
+    for i in range(mod.nums):
+        sp = spx[i] if i == 0 else sp + spx[i]
+        taps, w, left = _same_conv_taps(mod.convs[i], "Res2Conv1dReluBn")
+        scale, shift = _bn_fold(mod.bns[i])
+        sp = Sym(g, g.tdnn(sp.view, w, _np(mod.convs[i].bias), taps, left, act1="relu", scale=scale, shift=shift), 3)
+        outs.append(sp)
+    if mod.scale != 1:
+        outs.append(spx[mod.nums])
+    return sym_cat(outs, dim=1) if len(outs) > 1 else outs[0]
+
+
+def _handle_se_connect_linear(mod, x):
+    """SE_Connect of ecapa-tdnn-xvector.py:73-85: time mean -> Linear -> ReLU -> Linear -> sigmoid -> channel scale."""
+    g = x.graph
+    m = g.pool(x.view, stddev=False)
+    h = g.tdnn(m, _np(mod.linear1.weight)[:, :, None], _np(mod.linear1.bias), [0], 0, act1="relu")
+    s = g.tdnn(h, _np(mod.linear2.weight)[:, :, None], _np(mod.linear2.bias), [0], 0, act1="sigmoid")
+    return Sym(g, g.eltwise(x.view, seg_scale=s), 3)
+
+
+def _handle_attentive_stats_pool_plain(mod, x):
+    """AttentiveStatsPool of ecapa-tdnn-xvector.py:120-134: tanh(linear1 x) -> linear2 -> softmax over frames -> weighted mean,
+    sqrt(clamp(sum a x^2 - mean^2, 1e-9)).  No global context, no BatchNorm."""
+    g = x.graph
+    for c in (mod.linear1, mod.linear2):
+        if c.kernel_size != (1,) or c.stride != (1,) or c.groups != 1:
+            raise TraceError("AttentiveStatsPool: linear1 / linear2 must be kernel-size-1 Conv1d, got %r" % (c,))
+    h = g.tdnn(x.view, _np(mod.linear1.weight), _np(mod.linear1.bias), [0], 0, act1="tanh")
+    e = g.tdnn(h, _np(mod.linear2.weight), _np(mod.linear2.bias), [0], 0)
+    return Sym(g, g.attpool(x.view, e, eps=1e-9), 2)
+
+
 def _handle_se_connect(mod, x):
     """SE_Connect (ecapa_tdnn_xvector.py:97-111): AdaptiveAvgPool1d(1) -> Conv1d -> ReLU ->
-    Conv1d -> Sigmoid -> channel scale."""
+    Conv1d -> Sigmoid -> channel scale.  Two reference blueprints define a class of this name: the one with `linear1` / `linear2`
+    (and no `se`) is ecapa-tdnn-xvector.py's."""
     import torch
+    if not hasattr(mod, "se") and hasattr(mod, "linear1") and hasattr(mod, "linear2"):
+        return _handle_se_connect_linear(mod, x)
     seq = mod.se
     convs = [m for m in seq if isinstance(m, torch.nn.Conv1d)]
     if len(convs) != 2 or any(c.kernel_size != (1,) for c in convs):
@@ -793,6 +944,8 @@ def _handle_attentive_stats_pool(mod, x):
     [x ; mean ; std] is split: the x part runs per frame, the (mean, std) part is constant
     over an utterance and is hoisted into a per-utterance bias."""
     import torch
+    if not hasattr(mod, "attention") and hasattr(mod, "linear1") and hasattr(mod, "linear2"):      # ecapa-tdnn-xvector.py's class of this name
+        return _handle_attentive_stats_pool_plain(mod, x)
     att = mod.attention
     conv1, bn, conv2 = att[0], att[2], att[4]
     if not (isinstance(conv1, torch.nn.Conv1d) and isinstance(bn, torch.nn.BatchNorm1d) and isinstance(conv2, torch.nn.Conv1d)
@@ -817,6 +970,8 @@ def _handle_attentive_stats_pool(mod, x):
 MODULE_HANDLERS = {
     "SE_Connect": _handle_se_connect,
     "AttentiveStatsPool": _handle_attentive_stats_pool,
+    "Conv1dReluBn": _handle_conv1d_relu_bn,
+    "Res2Conv1dReluBn": _handle_res2_conv1d_relu_bn,
 }
 
 

@@ -106,7 +106,7 @@ class TopVirtualNnet(torch.nn.Module):
             function = getattr(type(self).extract_embedding, "__wrapped_body__", None)
         precision = getattr(self, "amd_precision", None) or _engine.default_precision()
         p = next(self.parameters())
-        key = (function, str(p.device), precision, _engine.default_flags(), _engine.gather_fuse_on(), _engine.mqpool_on(), getattr(self, "extracted_embedding", None), int(replica))
+        key = (function, str(p.device), precision, _engine.default_flags(), _engine.gather_fuse_on(), _engine.mqpool_on(), _engine.res2n_on(), getattr(self, "extracted_embedding", None), int(replica))
         eng = self._amd_engines.get(key)
         if eng is None:
             eng = _engine.compile_model(self, function=function, precision=precision)

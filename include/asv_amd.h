@@ -223,6 +223,24 @@ typedef struct asv_res2_desc {
 } asv_res2_desc_t;
 int asv_net_add_res2(asv_net_t *net, const asv_res2_desc_t *d);
 
+/* The Res2 chain over `width`-channel groups with any ONE group passing through, as one op (kernels_res2n.hip): the input view holds
+ * `groups` = n + 1 groups x_0 .. x_n; y_p = x_p for p = pass_group; the other groups, in ascending order, form the chain - the first
+ * y = BN(ReLU(TDNN_{[-d,0,d]}(x))), every later one y_g = BN(ReLU(TDNN(y_prev + x_g))); the output view receives cat(y_0 .. y_n).
+ * pass_group = n is Res2Conv1dReluBn of the reference's model/ecapa-tdnn-xvector.py, pass_group = 0 the wiring of asv_res2_desc_t.
+ * width: 64.  2 <= groups <= 8, 1 <= dilation <= 4.  16-bit precision modes only (the other modes keep one TDNN layer per branch).
+ * Every y is rounded to the element type where it is stored and the next input is round(round(y) + x), as in the per-layer path.
+ * weight: host f32 [groups - 1][width][width][2 d + 1], the convolved groups' dense kernels in chain order; bias (may be NULL: none) /
+ * scale / shift: host f32 [groups - 1][width].  A workgroup of the kernel produces ASV_RES2N_TILE_ROWS rows. */
+#define ASV_RES2N_TILE_ROWS 192
+typedef struct asv_res2n_desc {
+  uint32_t struct_size;
+  int32_t in_buf, in_ch_off;
+  int32_t out_buf, out_ch_off;
+  int32_t width, groups, pass_group, dilation;
+  const float *weight, *bias, *scale, *shift;
+} asv_res2n_desc_t;
+int asv_net_add_res2n(asv_net_t *net, const asv_res2n_desc_t *d);
+
 /* Elementwise: out = a (* seg_scale[segment]) (+ b) (+ c); any domain; views as above. */
 typedef struct asv_eltwise_desc {
   uint32_t struct_size;
@@ -321,6 +339,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream);
 #define ASV_KERNEL_CONV_NARROW_PERS 10 /* grid_conv_narrow_pers_kernel: the same layers as a persistent sliding-window kernel */
 #define ASV_KERNEL_CONV_WIDE 11   /* grid_conv_wide_kernel: C = 128 / 256 */
 #define ASV_KERNEL_CONV_S2D 12    /* grid_conv_s2d_kernel: the 128 -> 64 space-to-depth form of the stride-2 convolution */
+#define ASV_KERNEL_RES2N 13       /* kernels_res2n.hip: res2n_chain_kernel, the 64-wide Res2 chain as one launch */
 unsigned long long asv_kernel_launch_count(int which);
 
 /* Bytes of device memory currently held by the net (weights + activation arena). */
