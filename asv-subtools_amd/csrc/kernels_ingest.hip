@@ -1,0 +1,248 @@
+// Fused ingest of raw Kaldi features on the MI355X (gfx950): sliding-window mean (/ variance) normalisation AND voiced-frame
+// selection in ONE pass - the `apply-cmvn-sliding ... | select-voiced-frames ...` pipe the reference puts in front of its extractor
+// (pytorch/pipeline/extract_xvectors_for_pytorch.sh:105-118), in that order: every raw frame is normalised over its window of RAW
+// frames, then only the voiced ones are kept.
+//
+//     out[out_off[u] + rank_u(t)] = x[t] - mean(window_u(t))      (/ sqrt(max(var, 1e-10)) with norm_vars)      for voiced t
+//
+// asv_cmvn_sliding -> asv_select_frames (frontend.hip) compute the same in three launches: the normalised copy of the whole batch goes
+// to HBM and is read back, and a source-row index of every kept row goes through HBM too.  Here a raw element is read once per window
+// pass, only kept rows are written, and the rank of a frame is a ballot + popcount over the flag bytes.
+//
+// One wave per (utterance, segment of 32 frames, block of 64 columns); lane = column, so the 64 lanes read / write one row segment
+// of 4 * min(dim, 64) contiguous bytes.  The window rule and the accumulation order are those of cmvn_sliding_kernel (segments from
+// the utterance start, the first window summed directly in ascending order, then slide; f64 sums): without flags the output equals
+// asv_cmvn_sliding's bit for bit, whichever entry point prepared the features.
+
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "asv_internal.h"
+
+namespace asv {
+namespace {
+
+// Kaldi's SlidingWindowCmnInternal window of frame t (feat/feature-functions.cc): the rule of cmn_window_of in frontend.hip.
+__device__ __forceinline__ void ingest_window_of(int t, int n, int window, int min_window, int center, int *ws, int *we) {
+  int a, b;
+  if (center) { a = t - window / 2; b = a + window; } else { a = t - window; b = t + 1; }
+  if (a < 0) { b -= a; a = 0; }
+  if (!center && b > t) b = max(t + 1, min_window);
+  if (b > n) { a -= b - n; b = n; if (a < 0) a = 0; }
+  *ws = a; *we = b;
+}
+
+constexpr int kIngestSeg = 32;              // frames per wave: cmvn_sliding_kernel's kSlideSeg (part of the bit-for-bit contract)
+constexpr int kIngestSegsPerBlock = 4;      // waves per workgroup
+constexpr int kIngestAhead = 16;            // loads of the first window issued together
+
+// off: [frame_off (n_utts + 1) | out_off (n_utts + 1)].  voiced: one byte per raw frame, or nullptr (every frame is kept).
+// window <= 0: selection only (rows are copied as they are).
+__global__ __launch_bounds__(256) void ingest_frames_kernel(const float *__restrict__ in, const unsigned char *__restrict__ voiced, float *__restrict__ out,
+                                                            const long long *__restrict__ off, int n_utts, int dim, int window, int min_window,
+                                                            int center, int norm_vars) {
+  const int u = blockIdx.x, lane = threadIdx.x & 63, c = blockIdx.z * 64 + lane;
+  const long long f0 = off[u];
+  const int n = (int)(off[u + 1] - f0);
+  const int seg = blockIdx.y * kIngestSegsPerBlock + (threadIdx.x >> 6);
+  const int t0 = seg * kIngestSeg;
+  if (t0 >= n) return;                                                       // (wave-uniform: a wave is one segment)
+  const long long o0 = off[n_utts + 1 + u], o1 = off[n_utts + 2 + u];         // this utterance's rows of `out`
+  // which frames of the segment are kept, and how many voiced frames of the utterance lie in front of it
+  unsigned keep = 0xffffffffu;
+  long long row = o0 + t0;
+  if (voiced) {
+    // (all flag bytes of a step are loaded before the first ballot waits for one: a wave's time here is load latency)
+    const unsigned char *flag = voiced + f0;
+    const unsigned char mine = lane < kIngestSeg && t0 + lane < n ? flag[t0 + lane] : 0;
+    int before = 0;
+    for (int b = 0; b < t0; b += 256) {
+      unsigned char f[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[j] = b + j * 64 + lane < t0 ? flag[b + j * 64 + lane] : 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) before += __popcll(__ballot(f[j] != 0));
+    }
+    keep = (unsigned)__ballot(mine != 0);
+    row = o0 + before;
+  }
+  const int last = min(n - t0, kIngestSeg);
+  if (last < kIngestSeg) keep &= (1u << last) - 1u;
+  if (keep == 0 || c >= dim) return;
+  const int t1 = t0 + 32 - __clz(keep);                                       // one behind the last kept frame
+  const float *x = in + (size_t)f0 * dim + c;
+  float *y = out + c;
+  if (window <= 0) {
+    for (int t = t0; t < t1; ++t)
+      if ((keep >> (t - t0)) & 1u) {
+        if (row < o1) y[(size_t)row * dim] = x[(size_t)t * dim];            // (row >= o1: the flags hold more than the caller counted - never written)
+        ++row;
+      }
+    return;
+  }
+  int ws, we;
+  ingest_window_of(t0, n, window, min_window, center, &ws, &we);
+  double sum = 0.0, sumsq = 0.0;
+  // the first window, summed in ascending order - kIngestAhead independent loads in flight, the additions in the same order as one by one
+  int k = ws;
+  for (; k + kIngestAhead <= we; k += kIngestAhead) {
+    float ahead[kIngestAhead];
+#pragma unroll
+    for (int j = 0; j < kIngestAhead; ++j) ahead[j] = x[(size_t)(k + j) * dim];
+#pragma unroll
+    for (int j = 0; j < kIngestAhead; ++j) { const double v = ahead[j]; sum += v; sumsq += v * v; }
+  }
+  for (; k < we; ++k) { const double v = x[(size_t)k * dim]; sum += v; sumsq += v * v; }
+  for (int t = t0; t < t1; ++t) {
+    int a, b;
+    ingest_window_of(t, n, window, min_window, center, &a, &b);
+    // a window moves by at most one frame per step at either end: the (up to) three loads of a step are issued together, the
+    // arithmetic keeps its order - removals, then additions
+    const bool drop = ws < a, take = we < b;
+    const float x_drop = drop ? x[(size_t)ws * dim] : 0.0f, x_take = take ? x[(size_t)we * dim] : 0.0f, x_t = x[(size_t)t * dim];
+    if (drop) { const double v = x_drop; sum -= v; sumsq -= v * v; ++ws; }
+    while (ws < a) { const double v = x[(size_t)ws * dim]; sum -= v; sumsq -= v * v; ++ws; }
+    if (take) { const double v = x_take; sum += v; sumsq += v * v; ++we; }
+    while (we < b) { const double v = x[(size_t)we * dim]; sum += v; sumsq += v * v; ++we; }
+    if (!((keep >> (t - t0)) & 1u)) continue;                                 // the sums slide over unvoiced frames too
+    const double frames = (double)(we - ws);
+    double v = (double)x_t - sum / frames;
+    if (norm_vars) {
+      if (we - ws == 1) v = 0.0;
+      else {
+        double var = sumsq / frames - (sum / frames) * (sum / frames);
+        var = fmax(var, 1.0e-10);
+        v *= 1.0 / sqrt(var);
+      }
+    }
+    if (row < o1) y[(size_t)row * dim] = (float)v;
+    ++row;
+  }
+}
+
+// The two host offset arrays of a call, on the device.  Per calling thread: a ring of page-locked staging slots, each with its device
+// twin.  Unchanged contents (fixed batch shapes) reuse the last upload, changed ones take the next slot and copy asynchronously - the
+// host never waits for the stream either way (the extraction loops submit new offsets per batch, alternating between two streams).
+// Ordering is by events, whichever streams the calls of a thread use:
+//   * `uploaded` is recorded behind a slot's copy on the stream that made it; a call on ANOTHER stream that reuses the slot makes its
+//     stream wait for that event (a device-side wait) before its kernel reads the slot;
+//   * every stream that has launched a reader of a slot has its own `read` event there, recorded behind its latest launch; a slot is
+//     overwritten only after all of them have completed - in practice the launches of kRing changes of the offsets ago.
+// A thread's slots live as long as the process, like the offset cache of frontend.hip (a destructor would call into a HIP runtime that
+// may already be gone at exit).
+struct IngestOffsets {
+  static constexpr int kRing = 8;
+  struct Reader { hipStream_t stream; hipEvent_t read; };
+  struct Slot {
+    long long *host = nullptr, *dev = nullptr;
+    size_t cap = 0, count = 0;
+    hipStream_t stream = nullptr;          // the stream the current contents were copied on
+    hipEvent_t uploaded = nullptr;         // behind that copy
+    std::vector<Reader> readers;           // one event per stream that has read this slot since it was filled (events are kept and reused)
+    size_t n_readers = 0;                  // entries of `readers` in use
+  };
+  Slot slot[kRing];
+  int at = 0, device = -1;
+  static int drain(Slot &k) {              // every launch that reads the slot has finished
+    for (size_t i = 0; i < k.n_readers; ++i) ASV_HIP_CHECK(hipEventSynchronize(k.readers[i].read));
+    k.n_readers = 0;
+    return ASV_OK;
+  }
+  int get(const long long *a, const long long *b, size_t each, hipStream_t s, const long long **out) {
+    int cur = 0;
+    ASV_HIP_CHECK(hipGetDevice(&cur));
+    if (device != cur) {                                                      // (another device: start over there)
+      for (Slot &k : slot) {
+        { const int rc = drain(k); if (rc) return rc; }
+        for (Reader &r : k.readers) ASV_HIP_CHECK(hipEventDestroy(r.read));
+        if (k.uploaded) ASV_HIP_CHECK(hipEventDestroy(k.uploaded));
+        if (k.host) ASV_HIP_CHECK(hipHostFree(k.host));
+        if (k.dev) ASV_HIP_CHECK(hipFree(k.dev));
+        k = Slot();
+      }
+      device = cur;
+    }
+    const size_t count = 2 * each;
+    Slot &l = slot[at];
+    if (l.dev && l.count == count && memcmp(l.host, a, each * 8) == 0 && memcmp(l.host + each, b, each * 8) == 0) {
+      if (s != l.stream) ASV_HIP_CHECK(hipStreamWaitEvent(s, l.uploaded, 0));   // the copy was queued on another stream: this one waits for it
+      *out = l.dev;
+      return ASV_OK;
+    }
+    at = (at + 1) % kRing;
+    Slot &k = slot[at];
+    { const int rc = drain(k); if (rc) return rc; }
+    if (!k.uploaded) ASV_HIP_CHECK(hipEventCreateWithFlags(&k.uploaded, hipEventDisableTiming));
+    if (count > k.cap) {
+      if (k.host) ASV_HIP_CHECK(hipHostFree(k.host));
+      if (k.dev) ASV_HIP_CHECK(hipFree(k.dev));
+      k.host = k.dev = nullptr; k.cap = k.count = 0;
+      ASV_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&k.host), count * 16, hipHostMallocDefault));
+      ASV_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&k.dev), count * 16));
+      k.cap = count * 2;
+    }
+    memcpy(k.host, a, each * 8);
+    memcpy(k.host + each, b, each * 8);
+    k.count = 0;                                                              // (not reusable until the copy is queued and marked)
+    ASV_HIP_CHECK(hipMemcpyAsync(k.dev, k.host, count * 8, hipMemcpyHostToDevice, s));
+    ASV_HIP_CHECK(hipEventRecord(k.uploaded, s));
+    k.count = count;
+    k.stream = s;
+    *out = k.dev;
+    return ASV_OK;
+  }
+  // behind the launch on stream s that reads the current slot
+  int launched(hipStream_t s) {
+    Slot &k = slot[at];
+    size_t i = 0;
+    while (i < k.n_readers && k.readers[i].stream != s) ++i;
+    if (i == k.n_readers) {
+      if (i == k.readers.size()) {
+        Reader r = {s, nullptr};
+        ASV_HIP_CHECK(hipEventCreateWithFlags(&r.read, hipEventDisableTiming));
+        k.readers.push_back(r);
+      }
+      k.readers[i].stream = s;
+      ++k.n_readers;
+    }
+    ASV_HIP_CHECK(hipEventRecord(k.readers[i].read, s));
+    return ASV_OK;
+  }
+};
+thread_local IngestOffsets g_ingest_offs;
+
+}  // namespace
+}  // namespace asv
+
+using namespace asv;
+
+extern "C" int asv_ingest_frames(const float *feats, const unsigned char *voiced, const long long *frame_offsets, const long long *out_offsets, int n_utts,
+                                 int dim, int cmn_window, int min_window, int center, int norm_vars, float *out, void *stream) {
+  ASV_REQUIRE(feats && out && feats != out && frame_offsets && out_offsets && n_utts >= 1, "asv_ingest_frames: bad argument (in-place is not supported)");
+  ASV_REQUIRE(dim >= 1, "asv_ingest_frames: dim %d", dim);
+  ASV_REQUIRE(cmn_window <= 0 || center || (min_window > 0 && min_window <= cmn_window), "asv_ingest_frames: cmn_window %d / min_window %d", cmn_window,
+              min_window);
+  ASV_REQUIRE(frame_offsets[0] == 0 && out_offsets[0] == 0, "asv_ingest_frames: offsets must start at 0");
+  long long longest = 0;
+  for (int u = 0; u < n_utts; ++u) {
+    const long long frames = frame_offsets[u + 1] - frame_offsets[u], kept = out_offsets[u + 1] - out_offsets[u];
+    ASV_REQUIRE(frames >= 0 && kept >= 0, "asv_ingest_frames: offsets decrease at utterance %d", u);
+    ASV_REQUIRE(kept <= frames, "asv_ingest_frames: utterance %d keeps %lld of %lld frames", u, kept, frames);
+    ASV_REQUIRE(voiced || kept == frames, "asv_ingest_frames: utterance %d: without flags every frame is kept (%lld of %lld)", u, kept, frames);
+    longest = std::max(longest, frames);
+  }
+  if (out_offsets[n_utts] == 0) return ASV_OK;                               // nothing is kept: nothing is written
+  const long long blocks_y = (longest + kIngestSegsPerBlock * kIngestSeg - 1) / (kIngestSegsPerBlock * kIngestSeg);
+  ASV_REQUIRE(blocks_y <= 65535 && (dim + 63) / 64 <= 65535, "asv_ingest_frames: utterance of %lld frames / dim %d too large", longest, dim);
+  ASV_ON_OWNER(feats, "asv_ingest_frames");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const long long *d = nullptr;
+  { const int rc = g_ingest_offs.get(frame_offsets, out_offsets, (size_t)n_utts + 1, s, &d); if (rc) return rc; }
+  hipLaunchKernelGGL(ingest_frames_kernel, dim3((unsigned)n_utts, (unsigned)blocks_y, (unsigned)((dim + 63) / 64)), dim3(256), 0, s, feats, voiced, out, d,
+                     n_utts, dim, cmn_window, min_window, center, norm_vars);
+  ASV_HIP_CHECK(hipGetLastError());
+  return g_ingest_offs.launched(s);
+}

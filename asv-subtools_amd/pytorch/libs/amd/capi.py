@@ -189,6 +189,7 @@ SYMBOLS = [
     "asv_plda_transform", "asv_plda_llr_trials", "asv_eer", "asv_det_curve", "asv_min_dcf", "asv_cavg", "asv_score_norm", "asv_group_mean", "asv_two_cov_trials",
     "asv_plda_train", "asv_scatter_f64", "asv_class_scatter_f64",
     "asv_fbank_num_frames", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
+    "asv_ingest_frames",
 ]
 
 
@@ -270,6 +271,7 @@ def lib():
     L.asv_cmvn_sliding.argtypes = [vp, vp, C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp]
     L.asv_vad_energy.argtypes = [vp, C.POINTER(C.c_longlong), ci, ci, C.c_float, C.c_float, ci, C.c_float, vp, C.POINTER(C.c_longlong), vp]
     L.asv_select_frames.argtypes = [vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci, ci, vp, vp]
+    L.asv_ingest_frames.argtypes = [vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp, vp]
     L.asv_cmvn.argtypes = [vp, C.POINTER(C.c_longlong), ci, ci, ci, ci, C.c_float, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)          # AttributeError here = header/.so mismatch

@@ -202,3 +202,69 @@ def select_voiced(feats, voiced, frame_off, counts):
                                                 len(frame_off) - 1, feats.shape[1], C.c_void_p(out.data_ptr()),
                                                 C.c_void_p(torch.cuda.current_stream(feats.device).cuda_stream)), "asv_select_frames")
     return out, out_off
+
+
+def kept_offsets(voiced, frame_off):
+    """Host side of a selection: (kept frames per utterance int64 [n], their running sum int64 [n+1]) of host flags (any non-zero
+    byte keeps its frame)."""
+    frame_off = _off(frame_off)
+    rows = np.diff(frame_off)
+    counts = np.zeros(len(rows), dtype=np.int64)
+    some = rows > 0
+    if some.any():
+        # (sums over [start, next start): empty utterances have no width, so the starts of the others still delimit their frames)
+        kept = (np.asarray(voiced[int(frame_off[0]):int(frame_off[-1])]) != 0).view(np.uint8)
+        counts[some] = np.add.reduceat(kept, frame_off[:-1][some] - frame_off[0], dtype=np.int64)
+    kept_off = np.zeros(len(frame_off), dtype=np.int64)
+    np.cumsum(counts, out=kept_off[1:])
+    return counts, kept_off
+
+
+def ingest(feats, frame_off, voiced=None, cmn_window=0, min_window=100, center=True, norm_vars=False, out=None, kept_off=None):
+    """Raw packed device features -> the rows the extractor reads, in one launch (asv_ingest_frames): Kaldi apply-cmvn-sliding over all
+    raw frames (cmn_window > 0; the defaults center=True, norm_vars=False are those of the reference's
+    extract_xvectors_for_pytorch.sh:105-118), then select-voiced-frames (voiced: one flag per raw frame, non-zero = keep - a CUDA uint8
+    tensor as vad_energy returns it, or a host array; None keeps every frame, and the result equals cmvn_sliding's bit for bit).
+    cmn_window=0: selection only.  Returns (kept rows [sum kept, dim] f32 CUDA tensor - `out[:sum kept]` when `out` is given -, kept_off
+    int64 numpy [n+1]).  The kept counts come from the host flags, or from one small device-to-host copy for device flags; `kept_off`
+    hands them in where the caller has them already (no copy, no synchronisation)."""
+    import torch
+    frame_off = _off(frame_off)
+    n = len(frame_off) - 1
+    if feats.dim() != 2 or feats.dtype != torch.float32 or not feats.is_cuda or not feats.is_contiguous() or n < 1 or int(frame_off[-1]) != feats.shape[0]:
+        raise ValueError("ingest: feats must be a contiguous [frame_off[-1], dim] f32 CUDA tensor")
+    dev_flags = None
+    if voiced is not None:
+        if isinstance(voiced, torch.Tensor) and voiced.is_cuda:
+            if voiced.dtype != torch.uint8 or voiced.dim() != 1 or voiced.shape[0] < feats.shape[0] or not voiced.is_contiguous():
+                raise ValueError("ingest: voiced must hold one uint8 flag per raw frame")
+            dev_flags = voiced
+            if kept_off is None:
+                run = torch.zeros(feats.shape[0] + 1, dtype=torch.int64, device=feats.device)
+                torch.cumsum(voiced[:feats.shape[0]] != 0, 0, out=run[1:])
+                kept_off = run[torch.from_numpy(frame_off).to(feats.device)].cpu().numpy()
+        else:
+            host = np.ascontiguousarray(voiced.numpy() if isinstance(voiced, torch.Tensor) else voiced).astype(np.uint8, copy=False)
+            if host.ndim != 1 or host.shape[0] < feats.shape[0]:
+                raise ValueError("ingest: voiced must hold one uint8 flag per raw frame")
+            if kept_off is None:
+                kept_off = kept_offsets(host, frame_off)[1]
+            dev_flags = torch.from_numpy(host).to(feats.device)
+        if dev_flags.dtype != torch.uint8 or dev_flags.dim() != 1 or dev_flags.shape[0] < feats.shape[0] or not dev_flags.is_contiguous():
+            raise ValueError("ingest: voiced must hold one uint8 flag per raw frame")
+    kept_off = frame_off if kept_off is None else _off(kept_off)
+    if len(kept_off) != n + 1:
+        raise ValueError("ingest: kept_off must have one entry per utterance plus one")
+    rows = max(int(kept_off[-1]), 0)
+    if out is None:
+        out = torch.empty((rows, feats.shape[1]), dtype=torch.float32, device=feats.device)
+    elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != feats.shape[1] or out.shape[0] < rows:
+        raise ValueError("ingest: out must be a contiguous f32 CUDA tensor of at least [%d, %d]" % (rows, feats.shape[1]))
+    if rows == 0 and bool((np.diff(kept_off) == 0).all()):
+        return out[:0], kept_off                          # nothing is kept: no launch (an empty tensor has no address to hand over)
+    with torch.cuda.device(feats.device):
+        capi.check(capi.lib().asv_ingest_frames(C.c_void_p(feats.data_ptr()), C.c_void_p(dev_flags.data_ptr()) if dev_flags is not None else None,
+                                                _i64p(frame_off), _i64p(kept_off), n, feats.shape[1], int(cmn_window), int(min_window), int(bool(center)),
+                                                int(bool(norm_vars)), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(feats.device).cuda_stream)), "asv_ingest_frames")
+    return out[:rows], kept_off

@@ -13,12 +13,19 @@ handed on, with the same RuntimeWarning.  The fp32 reference has no such limit
 (/root/reference/pytorch/pipeline/onestep/extract_embeddings.py:70-83 writes whatever the f32 forward gives).
 """
 
+import collections
 import os
 import warnings
 
 import numpy as np
 
 from . import capi
+
+# What DeviceSets does to RAW features before the extractor reads them (asv_ingest_frames, one launch per batch): sliding-window CMN
+# with Kaldi's apply-cmvn-sliding options (cmn_window = 0: none) and, with flags=True, select-voiced-frames by one flag per raw frame
+# handed to submit().  The defaults are those of the reference's extract_xvectors_for_pytorch.sh:105-118.
+IngestOptions = collections.namedtuple("IngestOptions", "cmn_window min_window center norm_vars flags")
+IngestOptions.__new__.__defaults__ = (0, 100, True, False, False)
 
 
 class DeviceSets(object):
@@ -32,10 +39,14 @@ class DeviceSets(object):
         vectors = sets.finish(k)                       # blocks until the batch is done; range guard; [n, E] float32:
                                                        #   results='host': numpy view of page-locked memory (valid until the next submit(k))
                                                        #   results='device': a CUDA tensor of its own (stays valid)
+    ingest=IngestOptions(...): the rows the reader fills are RAW features - every set also holds a second device buffer and (flags=True)
+    a page-locked flag buffer with its device twin, and submit(k, offsets, frames, voiced) puts the fused CMN + selection launch between the
+    H2D copies and the extraction, on the same stream (no synchronisation: the kept counts come from the host flags).  The engine sees
+    the compacted rows and offsets; utterances that keep no frame are left out (finish() returns one vector per utterance that kept some).
     ASV_AMD_PIPELINE_ENGINES=1 keeps one engine on one stream (device-resident rate of two: +5 % x-vector, +9 % ECAPA, +19 %
     ResNet34-SE, profiles/r3h_streams.txt)."""
 
-    def __init__(self, model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", n_engines=2, warm=True):
+    def __init__(self, model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", n_engines=2, warm=True, ingest=None):
         import torch
         assert results in ("host", "device")
         self.torch = torch
@@ -65,6 +76,16 @@ class DeviceSets(object):
         self.host_np = [t.numpy() for t in self.host_in]
         self.dev_in = [torch.empty((batch_frames, dim), dtype=torch.float32, device=dev) for _ in range(n_sets)]
         self.status_host = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(n_sets)]
+        self.ingest = ingest
+        self.dev_raw = self.host_flags = self.flags_np = self.dev_flags = None          # ingest=None: nothing is allocated, nothing is launched
+        if ingest is not None:
+            if ingest.cmn_window > 0 and not ingest.center and not 0 < ingest.min_window <= ingest.cmn_window:
+                raise ValueError("sliding CMN without centring needs 0 < min_window <= cmn_window (got %d, %d)" % (ingest.min_window, ingest.cmn_window))
+            self.dev_raw = [torch.empty((batch_frames, dim), dtype=torch.float32, device=dev) for _ in range(n_sets)]
+            if ingest.flags:
+                self.host_flags = [torch.zeros(batch_frames, dtype=torch.uint8).pin_memory() for _ in range(n_sets)]
+                self.flags_np = [t.numpy() for t in self.host_flags]
+                self.dev_flags = [torch.empty(batch_frames, dtype=torch.uint8, device=dev) for _ in range(n_sets)]
         if results == "host":
             self.dev_out = [torch.empty((batch_utts, self.embed_dim), dtype=torch.float32, device=dev) for _ in range(n_sets)]
             self.host_out = [torch.empty((batch_utts, self.embed_dim), dtype=torch.float32).pin_memory() for _ in range(n_sets)]
@@ -82,6 +103,8 @@ class DeviceSets(object):
                 for e, eng in enumerate(self.engines):
                     with torch.cuda.stream(self.streams[e]):
                         eng.extract_device(self.dev_in[0][:int(offs[-1])], offs, max_chunk=self.max_chunk)
+                        if ingest is not None:         # (the ingest kernel's code object, and this thread's offset staging in the library)
+                            self._ingest(self.dev_in[0][:int(offs[-1])], offs.astype(np.int64), None, None, self.dev_raw[0])
                         if self.watch:
                             eng.status_async(self.status_host[0])
                 for st in self.streams:
@@ -93,10 +116,43 @@ class DeviceSets(object):
     def host_buffer(self, k):
         return self.host_np[k]
 
-    def submit(self, k, offsets, frames):
+    def flag_buffer(self, k):
+        """[batch_frames] uint8 numpy view of set k's page-locked flag buffer (ingest with flags): the reader fills it next to host_buffer(k)."""
+        return self.flags_np[k]
+
+    def _ingest(self, raw, raw_off, dev_flags, kept_off, out):
+        from . import frontend
+        o = self.ingest
+        return frontend.ingest(raw, raw_off, voiced=dev_flags, cmn_window=o.cmn_window, min_window=o.min_window, center=o.center,
+                               norm_vars=o.norm_vars, out=out, kept_off=kept_off)[0]
+
+    def submit(self, k, offsets, frames, voiced=None, kept_off=None):
+        """`voiced` (ingest with flags): one uint8 flag per raw row - flag_buffer(k)[:frames] as the reader filled it, or an array of its
+        own; `kept_off`: its per-utterance running sum where the caller has it already (frontend.kept_offsets)."""
         torch = self.torch
         assert self.pending[k] is None, "set %d still holds a batch: finish() it first" % k
         n = len(offsets) - 1
+        raw_off = None
+        if self.ingest is not None:
+            raw_off = np.ascontiguousarray(offsets, dtype=np.int64)
+            if self.ingest.flags:
+                if voiced is None:
+                    raise ValueError("these buffer sets select voiced frames: submit() needs the flags of the batch")
+                from . import frontend
+                voiced = np.asarray(voiced)
+                if voiced.dtype != np.uint8 or voiced.ndim != 1 or voiced.shape[0] < int(raw_off[-1]):
+                    raise ValueError("voiced must hold one uint8 flag per raw frame")
+                if kept_off is None:
+                    kept_off = frontend.kept_offsets(voiced, raw_off)[1]
+                kept_off = np.ascontiguousarray(kept_off, dtype=np.int64)
+                counts = np.diff(kept_off)
+                # the engine rejects empty utterances: those that keep nothing are not handed to it
+                offsets = np.concatenate((kept_off[:1], kept_off[1:][counts > 0])).astype(np.int32)
+                n = len(offsets) - 1
+                if n == 0:
+                    return None                              # nothing of this batch is kept: nothing is copied or launched, finish(k) gives None
+            elif voiced is not None:
+                raise ValueError("these buffer sets were made without flags (IngestOptions.flags)")
         e = self._next_engine                            # consecutive batches alternate between the engines (each on its own stream: in
         self._next_engine = (e + 1) % len(self.engines)  # order, so the status word copied behind a batch is that batch's alone)
         out = None
@@ -112,13 +168,27 @@ class DeviceSets(object):
         import time
         t = [time.perf_counter()]
         with torch.cuda.device(self.dev), torch.cuda.stream(self.streams[e]):
-            if isinstance(frames, np.ndarray):           # one utterance longer than a whole batch buffer: a pageable copy of its own
+            own = isinstance(frames, np.ndarray)
+            if own:                                      # one utterance longer than a whole batch buffer: a pageable copy of its own
                 feats = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.float32)).to(self.dev)
             else:
-                feats = self.dev_in[k][:frames]
+                feats = (self.dev_in if self.ingest is None else self.dev_raw)[k][:frames]
                 feats.copy_(self.host_in[k][:frames], non_blocking=True)
+            flags = None
+            if self.ingest is not None and self.ingest.flags:
+                rows = feats.shape[0]
+                if own:
+                    flags = torch.from_numpy(np.ascontiguousarray(voiced[:rows])).to(self.dev)
+                else:
+                    if voiced.ctypes.data != self.flags_np[k].ctypes.data:
+                        self.flags_np[k][:rows] = voiced[:rows]
+                    flags = self.dev_flags[k][:rows]
+                    flags.copy_(self.host_flags[k][:rows], non_blocking=True)
             self.h2d[k].record()
             t.append(time.perf_counter())
+            if self.ingest is not None:                  # raw rows -> normalised kept rows, compacted: what the engine (and a range re-run) reads
+                feats = self._ingest(feats, raw_off, flags, kept_off, None if own else self.dev_in[k])
+                t.append(time.perf_counter())
             if self.results == "host":
                 out = self.dev_out[k][:n]
             self.engines[e].extract_device(feats, offsets, max_chunk=self.max_chunk, out=out)
@@ -129,7 +199,7 @@ class DeviceSets(object):
                 self.engines[e].status_async(self.status_host[k])
             self.done[k].record()
             t.append(time.perf_counter())
-        for i, name in enumerate(("h2d", "extract", "d2h")):
+        for i, name in enumerate(("h2d", "extract", "d2h") if self.ingest is None else ("h2d", "ingest", "extract", "d2h")):
             self.submit_seconds[name] = self.submit_seconds.get(name, 0.0) + t[i + 1] - t[i]
         self.submitted += 1
         self.pending[k] = (feats, np.array(offsets, dtype=np.int32), out, n, e, self.submitted)

@@ -15,6 +15,13 @@ calling shell script greps the log for "Error".
 Extra options: --batch-frames / --batch-utts bound a batch; --verbose true restores the reference's
 per-utterance "Process utterance for key ..." line (a measurable cost at >100k utterances/s).
 
+Raw features: the reference's shell script puts `apply-cmvn-sliding ... scp:feats.scp ark:- | select-voiced-frames ark:-
+scp,s,cs:vad.scp ark:- |` in front of this script (pipeline/extract_xvectors_for_pytorch.sh:105-118).  --cmn-window N
+[--cmn-center true|false --cmn-norm-vars true|false --cmn-min-window N] and --vad-scp vad.scp do both on the device, in one
+launch per batch between the H2D copy and the extraction (libs.amd.pipeline.DeviceSets, asv_ingest_frames), so the
+feats-rspecifier can be the raw `scp:feats.scp`.  As select-voiced-frames does, an utterance without a VAD entry, with a VAD
+vector of another length than its matrix, or without a voiced frame is skipped with a WARNING line on stderr.
+
 Multi-GPU (--sharded true, launched as `python -m torch.distributed.run --nproc-per-node N ... extract_embeddings.py ...`, one
 process per GPU): replaces the reference's `nj` jobs over a length-balanced split of feats.scp and the final
 `cat xvector.JOB.scp` (pipeline/extract_xvectors_for_pytorch.sh:90-100,125-151; splitDataByLength.sh:44-80).  Every rank reads
@@ -54,13 +61,165 @@ def get_args(argv=None):
     parser.add_argument("--sharded", type=str, default="false", choices=["true", "false"],
                         help="One process per GPU under torch.distributed.run: shard the scp by length, all-gather, rank 0 writes.")
     parser.add_argument("--utt2num-frames", type=str, default="", help="Kaldi utt2num_frames of the scp (sharded mode; default: read the matrix headers).")
+    parser.add_argument("--cmn-window", type=int, default=0, help="Sliding-window CMN on the device (apply-cmvn-sliding --cmn-window); 0 = off.")
+    parser.add_argument("--cmn-center", type=str, default="true", choices=["true", "false"], help="apply-cmvn-sliding --center.")
+    parser.add_argument("--cmn-norm-vars", type=str, default="false", choices=["true", "false"], help="apply-cmvn-sliding --norm-vars.")
+    parser.add_argument("--cmn-min-window", type=int, default=100, help="apply-cmvn-sliding --min-cmn-window; only read when not centred.")
+    parser.add_argument("--vad-scp", type=str, default="", help="Kaldi scp of per-frame VAD vectors: select-voiced-frames on the device.")
     parser.add_argument("model_path", metavar="model-path", type=str, help="The model used to extract embeddings.")
     parser.add_argument("feats_rspecifier", metavar="feats-rspecifier", type=str, help="")
     parser.add_argument("vectors_wspecifier", metavar="vectors-wspecifier", type=str, help="")
     return parser.parse_args(argv)
 
 
-def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=False, reader=None):
+def ingest_options(args):
+    """libs.amd.pipeline.IngestOptions of the command line, or None when the features are read as they are."""
+    from libs.amd.pipeline import IngestOptions
+    if args.vad_scp and utils.to_bool(args.sharded):
+        raise ValueError("--sharded true does not take --vad-scp: balancing the shards by voiced counts and dropping entries from the gather "
+                         "are not built; run without --sharded, or select the voiced frames beforehand")
+    if args.cmn_window < 0:
+        raise ValueError("--cmn-window %d: pass a window length in frames, or 0 for none" % args.cmn_window)
+    center = utils.to_bool(args.cmn_center)
+    if args.cmn_window > 0 and not center and not 0 < args.cmn_min_window <= args.cmn_window:
+        raise ValueError("--cmn-center false needs 0 < --cmn-min-window <= --cmn-window (got %d, %d)" % (args.cmn_min_window, args.cmn_window))
+    if args.cmn_window == 0 and not args.vad_scp:
+        return None
+    return IngestOptions(args.cmn_window, args.cmn_min_window, center, utils.to_bool(args.cmn_norm_vars), bool(args.vad_scp))
+
+
+class VadTable(object):
+    """The per-frame VAD vectors of a Kaldi scp (`vad.scp`, written by compute-vad-decision), looked up by utterance key: the second
+    input of select-voiced-frames.  flags_for() fills the uint8 flag buffer of one batch and applies that program's rules: a frame is
+    kept when its flag is non-zero; a flag that is neither 0 nor 1 is an error (Kaldi asserts it); an utterance with no entry, with a
+    vector of another length than its matrix has rows, or without a voiced frame is skipped with one WARNING line on stderr.
+    The scp is parsed once.  A plain binary float vector entry 'file.ark:offset' is `\0B FV \4 <int32 dim>` + 4 * dim bytes, and dim has
+    to equal the matrix's row count, which is known: the header and the 4 * T payload bytes of every entry of a batch are read in one
+    call into libasv_io.so (native threads, the GIL released), the payload straight into the batch's float buffer.  Everything else - text, double vectors, pipes, a read that runs into
+    the end of the file - goes through kaldi_io.read_vec_flt."""
+
+    def __init__(self, path, threads=4, warn=None):
+        from libs.support import native_io
+        self.entries = read_scp(path)
+        self.threads = max(1, int(threads))
+        self.skipped = 0
+        self._warn = warn if warn is not None else (lambda line: print(line, file=sys.stderr))
+        self._fds = {}
+        self._lut = None                                   # descriptor per path, once all are open
+        n = len(self.entries)
+        keys = self.entries.keys() if hasattr(self.entries, "plain_index") else [k for k, _ in self.entries]
+        self.index = {k: i for i, k in enumerate(keys)}
+        self._file = np.full(n, -1, dtype=np.int64)        # entry -> index into self._paths of a plain 'file:offset' entry, or -1
+        self._offset = np.zeros(n, dtype=np.int64)
+        self._paths = []
+        if native_io.lib() is None:
+            return
+        if hasattr(self.entries, "plain_index"):
+            pid, poff, paths = self.entries.plain_index()
+            remap = np.full(len(paths) + 1, -1, dtype=np.int64)
+            for j, name in enumerate(paths):
+                if os.path.isfile(name):
+                    remap[j] = len(self._paths)
+                    self._paths.append(name)
+            self._file[:] = remap[np.asarray(pid[:n])]
+            self._offset[:] = np.where(self._file >= 0, np.asarray(poff[:n]), 0)
+        else:
+            ids = {}
+            for i, (_, rx) in enumerate(self.entries):
+                name, sep, o = rx.rpartition(":")
+                if sep and o.isdigit():
+                    if name not in ids:
+                        ids[name] = len(self._paths) if os.path.isfile(name) else -1
+                        if ids[name] >= 0:
+                            self._paths.append(name)
+                    self._file[i], self._offset[i] = ids[name], int(o)
+
+    def close(self):
+        for fd in self._fds.values():
+            os.close(fd)
+        self._fds.clear()
+
+    def _descriptors(self):
+        if self._lut is None:
+            for j, name in enumerate(self._paths):
+                self._fds[j] = os.open(name, os.O_RDONLY)
+            self._lut = np.asarray([self._fds[j] for j in range(len(self._paths))], dtype=np.int32)
+        return self._lut
+
+    def flags_for(self, keys, offsets, flags):
+        """flags[offsets[i]:offsets[i + 1]] = the 0 / 1 flags of utterance keys[i] (zeros for a skipped one), for every i.
+        Returns (the keys that keep at least one frame, kept_off int64 [n + 1]: running sum of the kept frames per utterance)."""
+        from libs.amd.frontend import kept_offsets
+        from libs.support import native_io
+        n = len(keys)
+        off = np.asarray(offsets, dtype=np.int64)
+        rows = np.diff(off)
+        total = int(off[-1])
+        flags[:total] = 0
+        entry = np.asarray([self.index.get(key, -1) for key in keys], dtype=np.int64)
+        cause = [None] * n                                   # why an utterance is skipped
+        for i in np.flatnonzero(entry < 0):
+            cause[i] = "no VAD entry"
+        have = entry >= 0
+        fast = np.flatnonzero(have & (self._file[np.where(have, entry, 0)] >= 0)) if len(self._paths) else np.zeros(0, dtype=np.int64)
+        handled = np.zeros(n, dtype=bool)                    # read (or refused for its length) by the batched reads below
+        if len(fast):
+            # ONE native call, two positioned reads per entry: its 10 header bytes into head[j], its 4 T payload bytes straight to
+            # values[off[i]:off[i + 1]] - frame g of the batch is values[g]
+            head = np.zeros((len(fast), 16), dtype=np.uint8)
+            values = np.zeros(total, dtype=np.float32)
+            e = entry[fast]
+            fds, pos = self._descriptors()[self._file[e]], self._offset[e]
+            some = rows[fast] > 0
+            try:
+                native_io.pread_batch(np.concatenate((fds, fds[some])), np.concatenate((pos, pos[some] + 10)),
+                                      np.concatenate((np.full(len(fast), 10, dtype=np.int64), 4 * rows[fast][some])), 0,
+                                      np.concatenate((head.ctypes.data + 16 * np.arange(len(fast), dtype=np.int64), values.ctypes.data + 4 * off[fast][some])),
+                                      threads=self.threads)
+            except OSError:
+                # a read ran into the end of its file (a vector shorter than its matrix, last in its archive): nothing of this call
+                # is used, every entry of the group goes through read_vec_flt below, which names the short one
+                fast = fast[:0]
+        if len(fast):
+            binary = (head[:, 0] == 0) & (head[:, 1] == ord("B")) & (head[:, 2] == ord("F")) & (head[:, 3] == ord("V")) & (head[:, 4] == ord(" ")) & (head[:, 5] == 4)
+            dims = np.ascontiguousarray(head[:, 6:10]).view("<i4").ravel()
+            fits = binary & (dims == rows[fast])
+            for i, d in zip(fast[binary & ~fits].tolist(), dims[binary & ~fits].tolist()):
+                cause[i] = "its VAD vector has %d entries, its feature matrix %d rows" % (d, rows[i])
+            handled[fast[binary]] = True                     # (not a plain binary float vector: read_vec_flt below)
+            good = np.zeros(n, dtype=bool)
+            good[fast[fits]] = True
+            if not good.all():
+                values[~np.repeat(good, rows)] = 0.0         # what was read for the others is not a flag vector of this length
+            voiced = values != 0.0
+            bad = voiced & (values != 1.0)
+            if bad.any():
+                g = int(np.flatnonzero(bad)[0])
+                i = int(np.searchsorted(off, g, side="right")) - 1
+                raise ValueError("the VAD vector of %s holds %r at frame %d: select-voiced-frames takes 0 or 1 only" % (keys[i], float(values[g]), g - int(off[i])))
+            flags[:total] = voiced
+        slow = np.flatnonzero(have & ~handled)
+        for i in slow.tolist():
+            v = np.asarray(kaldi_io.read_vec_flt(self.entries[int(entry[i])][1]))
+            if v.shape[0] != rows[i]:
+                cause[i] = "its VAD vector has %d entries, its feature matrix %d rows" % (v.shape[0], rows[i])
+                continue
+            if ((v != 0.0) & (v != 1.0)).any():
+                g = int(np.flatnonzero((v != 0.0) & (v != 1.0))[0])
+                raise ValueError("the VAD vector of %s holds %r at frame %d: select-voiced-frames takes 0 or 1 only" % (keys[i], float(v[g]), g))
+            flags[int(off[i]):int(off[i + 1])] = v != 0.0
+        counts, kept_off = kept_offsets(flags, off)
+        empty = np.flatnonzero(counts == 0)
+        if len(empty) == 0:
+            return list(keys), kept_off
+        for i in empty.tolist():
+            self.skipped += 1
+            self._warn("WARNING: skipping utterance %s: %s" % (keys[i], cause[i] if cause[i] is not None else "no voiced frame"))
+        drop = set(empty.tolist())
+        return [key for i, key in enumerate(keys) if i not in drop], kept_off
+
+
+def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=False, reader=None, ingest=None, vad=None):
     """feature ark stream -> embedding ark stream, pipelined in three stages over two buffer sets:
       reader thread   next packed batch -> pinned host buffer   (kaldi_io.IndexedArkReader for ark files - native index + batched reads -,
                       kaldi_io.PackedArkReader for pipes: block reads, no per-utterance arrays; ScpGroupReader for `scp:` input)
@@ -69,7 +228,11 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
       writer          previous batch's vectors -> one write() of the assembled ark bytes
     so reading batch i+1 and writing batch i-1 overlap the device work of batch i.  Output order = input order.
     A batch whose activations left the range of the default mode's operand split is re-run with bf16 halves before it is written
-    (DeviceSets.finish; the reference's f32 forward has no such limit)."""
+    (DeviceSets.finish; the reference's f32 forward has no such limit).
+    `ingest` (IngestOptions): the input is RAW features - sliding CMN and, with `vad` (a VadTable), voiced-frame selection run on the
+    device in front of the extraction; a second reader stage (its own thread, so that the VAD reads of group i overlap the matrix reads of
+    group i + 1) fetches a group's VAD vectors into the set's page-locked flag buffer.  Vectors are written for the utterances that keep
+    at least one frame."""
     import queue
     import threading
     from libs.amd.pipeline import DeviceSets
@@ -89,7 +252,7 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
     # 128 / 256 rows: a group is cut so that its ROWS fit --batch-frames (65 536 = 256 tiles of 256 rows: 321 utterances of 200 frames
     # fill whole rounds of tiles on the 256 CUs; 327 - the frames alone - were 2.04 rounds of 128-row tiles, i.e. three)
     reader.row_pad = 4
-    sets = DeviceSets(model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host")
+    sets = DeviceSets(model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", ingest=ingest)
     free_sets, batches = queue.Queue(), queue.Queue()
     for k in range(sets.n_sets):
         free_sets.put(k)
@@ -99,24 +262,52 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
             while True:
                 k = free_sets.get()
                 keys, offsets, frames = reader.read_group(sets.host_buffer(k), batch_utts)
-                batches.put((k, keys, offsets, frames))
+                staged.put((k, keys, offsets, frames, None))
                 if not keys:
                     return
         except BaseException as e:                    # surfaces in the consumer
-            batches.put(e)
+            staged.put(e)
 
-    t = threading.Thread(target=produce, daemon=True)
-    t.start()
-    n_done, in_flight = 0, None
+    def attach_flags():
+        # second stage of the reader (its own thread: the VAD reads of group i overlap the matrix reads of group i + 1)
+        try:
+            while True:
+                item = staged.get()
+                if isinstance(item, BaseException):
+                    batches.put(item)
+                    return
+                k, keys, offsets, frames, _ = item
+                voiced = None
+                if keys:
+                    a = clock()
+                    flags = np.zeros(frames.shape[0], dtype=np.uint8) if isinstance(frames, np.ndarray) else sets.flag_buffer(k)[:frames]
+                    voiced = (flags,) + vad.flags_for(keys, offsets, flags)
+                    spent["vad"] += clock() - a
+                batches.put((k, keys, offsets, frames, voiced))
+                if not keys:
+                    return
+        except BaseException as e:
+            batches.put(e)
 
     clock = time.perf_counter
     spent = {"reader": 0.0, "submit": 0.0, "device": 0.0, "write": 0.0}       # where the consumer thread's time goes (ASV_AMD_REPORT_TIMING)
+    staged = batches
+    if vad is not None:
+        spent["vad"] = 0.0                                                    # ... and what the VAD reads take on their own thread
+        staged = queue.Queue()
+        threading.Thread(target=attach_flags, daemon=True).start()
+    t = threading.Thread(target=produce, daemon=True)
+    t.start()
+    n_done, in_flight = 0, None
 
     def finish(item):
         k, keys = item
         a = clock()
         vectors = sets.finish(k)                      # waits for the batch; range guard (re-run on the bf16-halves twin if flagged)
         b = clock()
+        if vectors is None:                           # no utterance of the batch kept a frame: nothing was submitted
+            free_sets.put(k)
+            return 0
         if verbose:
             for key in keys:
                 print("Process utterance for key {0}".format(key))
@@ -134,10 +325,14 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
         spent["reader"] += b - a
         if isinstance(item, BaseException):
             raise item
-        k, keys, offsets, frames = item
+        k, keys, offsets, frames, voiced = item
         if not keys:
             break
-        sets.submit(k, offsets, frames)
+        if voiced is not None:
+            flags, keys, kept_off = voiced            # (the keys that keep a frame: one vector each)
+            sets.submit(k, offsets, frames, voiced=flags, kept_off=kept_off)
+        else:
+            sets.submit(k, offsets, frames)
         spent["submit"] += clock() - b
         if in_flight is not None:
             n_done += finish(in_flight)
@@ -787,7 +982,7 @@ def run_sharded(args, model, max_chunk, verbose):
     # the device side is the stream path's: page-locked input buffers the loader reads the files INTO, asynchronous H2D, two engines
     # on two HIP streams, the range status word behind every batch (libs.amd.pipeline.DeviceSets) - until round 5 this path copied a
     # pageable batch synchronously into ONE engine and never looked at the status word
-    sets = DeviceSets(model, args.batch_frames, args.batch_utts, engine.feat_dim, max_chunk, n_sets=3, results="device")
+    sets = DeviceSets(model, args.batch_frames, args.batch_utts, engine.feat_dim, max_chunk, n_sets=3, results="device", ingest=ingest_options(args))
     loader = ScpBatchLoader(entries, threads=_reader_threads(),
                             buffers=[sets.host_buffer(k) for k in range(sets.n_sets)], before_fill=sets.input_consumed)
     # all headers in one native call (also what lengths() below reads) - under several ranks each reads 1 / world of them and one
@@ -851,6 +1046,7 @@ def main(argv=None):
             raise RuntimeError("asv-subtools_amd extracts on a ROCm device only (--use-gpu=true); there is no CPU path")
 
         sharded = utils.to_bool(args.sharded)
+        ingest = ingest_options(args)                 # (refuses --sharded true --vad-scp before anything is set up)
         if sharded:
             import torch.distributed as dist
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # dmabuf IPC for RCCL on these hosts
@@ -893,6 +1089,7 @@ def main(argv=None):
         verbose = utils.to_bool(args.verbose)
 
         n_done = 0
+        vad = VadTable(args.vad_scp, threads=_reader_threads()) if args.vad_scp else None
         if sharded:
             import torch.distributed as dist
             n_done = run_sharded(args, model, max_chunk, verbose)
@@ -905,13 +1102,19 @@ def main(argv=None):
             reader = ScpGroupReader(read_scp(args.feats_rspecifier), threads=_reader_threads())
             try:
                 with kaldi_io.open_or_fd(args.vectors_wspecifier, "wb") as w:
-                    n_done = extract_stream(model, None, w, args.batch_frames, args.batch_utts, max_chunk, verbose, reader=reader)
+                    n_done = extract_stream(model, None, w, args.batch_frames, args.batch_utts, max_chunk, verbose, reader=reader, ingest=ingest, vad=vad)
             finally:
                 reader.close()
         else:
             with kaldi_io.open_or_fd(args.feats_rspecifier, "rb") as r, kaldi_io.open_or_fd(args.vectors_wspecifier, "wb") as w:
-                n_done = extract_stream(model, r, w, args.batch_frames, args.batch_utts, max_chunk, verbose)
-        print("Extracted {0} embeddings.".format(n_done))
+                n_done = extract_stream(model, r, w, args.batch_frames, args.batch_utts, max_chunk, verbose, ingest=ingest, vad=vad)
+        if vad is None:
+            print("Extracted {0} embeddings.".format(n_done))
+        else:
+            vad.close()
+            print("Extracted {0} embeddings; skipped {1} utterances (no usable VAD vector or no voiced frame).".format(n_done, vad.skipped))
+            if n_done == 0 and vad.skipped > 0:
+                raise RuntimeError("every utterance was skipped (select-voiced-frames exits 1 when it wrote nothing)")
     except BaseException as e:
         if not isinstance(e, KeyboardInterrupt):
             traceback.print_exc()

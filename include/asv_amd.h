@@ -534,6 +534,19 @@ int asv_vad_energy(const float *feats, const long long *frame_offsets, int n_utt
  * [n_utts+1] running sum of voiced_counts; out: device [out_offsets[n_utts]][dim]. */
 int asv_select_frames(const float *feats, const unsigned char *voiced, const long long *frame_offsets,
                       const long long *out_offsets, int n_utts, int dim, float *out, void *stream);
+/* The two stages above in one pass over raw features: sliding-window normalisation over ALL raw frames, then only the
+ * voiced rows are written (the order of the Kaldi pipe `apply-cmvn-sliding ... | select-voiced-frames ...`), with no
+ * normalised copy of the batch and no row index in between.  voiced: device bytes, one per raw frame (non-zero = keep), or
+ * NULL: every frame is kept and the result equals asv_cmvn_sliding's bit for bit.  cmn_window <= 0: selection only, rows
+ * are copied as they are (min_window / center / norm_vars are then not read).  frame_offsets / out_offsets: host int64
+ * [n_utts+1], both from 0; out_offsets = running sum of the kept counts (an utterance may keep nothing, or be empty);
+ * out: device [out_offsets[n_utts]][dim], must not alias feats.  Negative return: dim < 1, decreasing offsets, an
+ * utterance that keeps more rows than it has (or, without flags, not all of them), a causal window (center = 0) with
+ * min_window outside [1, cmn_window].  Rows beyond an utterance's span of out are never written, whatever the flags hold.
+ * The offsets are staged by the library: no stream synchronisation, the caller's arrays may be reused on return. */
+int asv_ingest_frames(const float *feats, const unsigned char *voiced, const long long *frame_offsets,
+                      const long long *out_offsets, int n_utts, int dim, int cmn_window, int min_window, int center,
+                      int norm_vars, float *out, void *stream);
 /* Per-utterance mean / variance normalisation of every column, in place (kaldi_features.py:11-66
  * InputSequenceNormalization: mean over the frames, unbiased std floored at eps).  frame_offsets: host int64 [n_utts+1]. */
 int asv_cmvn(float *feats, const long long *frame_offsets, int n_utts, int dim, int mean_norm, int std_norm, float eps,
