@@ -345,6 +345,23 @@ int launch_lde_pool(const void *x, int ldx, int channels, int rows, const float 
                     const int32_t *seg_row0, const int32_t *seg_len, int segments, float *out, int ld_out, int et, hipStream_t s);
 int launch_eltwise(const EltwiseKernelParams &p, int et, hipStream_t s);
 
+// float64 score matrices of the PLDA back-end (kernels_score_matrix.hip): C[i][j] = sum_k A[i][k] B[j][k] + row[i] + col[j] on the f64
+// matrix instruction.  A [m][kp], B [n][kp] float64 with kp a multiple of kScoreMatrixKChunk and zeros beyond the real K (the
+// preparation kernels write them), row [m], col [n] or nullptr, C dense [m][n] float (the LLR) or double (two-covariance).
+constexpr int kScoreMatrixKChunk = 16;
+template <typename TOut>
+int launch_score_matrix(const double *A, int m, const double *B, int n, int kp, const double *row, const double *col, TOut *C, hipStream_t s);
+// operands of the Kaldi-style LLR matrix: A / row from (enroll, psi, enroll_n or nullptr), B from test; K = 2 dim
+int launch_plda_llr_prep(const float *enroll, int n_enroll, const float *test, int n_test, int dim, const float *psi, const int32_t *enroll_n, double *A, double *B,
+                         int kp, double *row, hipStream_t s);
+// one side of the two-covariance matrix from x, X Lambda, X Gamma and c: [XL | x] and its row term (enrol) or [x | XL] and its column term (test)
+int launch_two_cov_prep(const float *x, int n, int dim, const double *xl, const double *xg, const double *c, bool enroll_side, double *out, int kp, double *bias,
+                        hipStream_t s);
+#ifdef ASV_WITH_ABLATION
+// developer build only: the same prepared operands through the vector-unit gemm64_kernel of plda_train.hip and a row add (`scratch`: m * n float64)
+int score_matrix_valu_f32(const double *A, int m, const double *B, int n, int kp, const double *row, double *scratch, float *C, hipStream_t s);
+#endif
+
 // weight packing (host): dense checkpoint kernel -> [cout_pad][n_taps][cin_pad] in element type
 void pack_tdnn_weight(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps,
                       int n_taps, int cout_pad, int cin_pad, int et, void *dst);

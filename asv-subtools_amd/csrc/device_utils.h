@@ -193,6 +193,13 @@ __device__ __forceinline__ void split_mx(float v0, float v1, uint32_t &hi16, int
   lo8 = __builtin_amdgcn_cvt_pk_bf8_f32(r0 * 2048.0f, r1 * 2048.0f, lo8, SEL);
 }
 
+// sum of a float64 value over the 64 lanes of a wave (every lane gets the total; the order of the additions is fixed)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
 // tag arguments of the chain kernels' generic lambdas: TrYes = the matrix instruction with swapped operands (lane = channel)
 struct TrNo { static constexpr bool value = false; };
 struct TrYes { static constexpr bool value = true; };

@@ -236,11 +236,11 @@ struct DevBuf {
 };
 
 template <typename TA, typename TB>
-int gemm64(Gemm64Params p, int batches, DevBuf &partials, size_t &partial_cap, hipStream_t s) {
+int gemm64(Gemm64Params p, int batches, DevBuf &partials, size_t &partial_cap, hipStream_t s, bool allow_split = true) {
   // split K when the tile grid alone cannot fill the device
   const int tiles = ((p.m + 63) / 64) * ((p.n + 63) / 64) * batches;
   int ksplit = 1;
-  if (tiles < 512 && p.k > 2048) ksplit = std::min(64, std::max(1, std::min(1024 / tiles, p.k / 1024)));
+  if (allow_split && tiles < 512 && p.k > 2048) ksplit = std::min(64, std::max(1, std::min(1024 / tiles, p.k / 1024)));
   p.ksplit = ksplit;
   double *c = p.c;
   const double alpha = p.alpha, beta = p.beta;
@@ -266,6 +266,30 @@ int gemm64(Gemm64Params p, int batches, DevBuf &partials, size_t &partial_cap, h
 }
 
 }  // namespace
+
+#ifdef ASV_WITH_ABLATION
+namespace {
+// c[i][j] = (float)(p[i][j] + row[i])
+__global__ __launch_bounds__(256) void row_add_f32_kernel(const double *p, const double *row, long long m, int n, float *c) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e < m * n) c[e] = (float)(p[e] + row[e / n]);
+}
+}  // namespace
+// developer build only (asv_internal.h): the A/B partner of score_matrix_kernel on the vector unit
+int score_matrix_valu_f32(const double *A, int m, const double *B, int n, int kp, const double *row, double *scratch, float *C, hipStream_t s) {
+  Gemm64Params g; memset(&g, 0, sizeof(g));
+  g.a = A; g.sa_i = kp; g.sa_k = 1; g.b = B; g.sb_k = 1; g.sb_j = kp; g.c = scratch;
+  g.m = m; g.n = n; g.k = kp; g.ldc = n; g.alpha = 1.0; g.beta = 0.0;
+  DevBuf partials;
+  size_t partial_cap = 0;
+  int rc = gemm64<double, double>(g, 1, partials, partial_cap, s, false);      // no split-K: it is not part of this measurement
+  if (rc) return rc;
+  const long long e = (long long)m * n;
+  hipLaunchKernelGGL(row_add_f32_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, s, scratch, row, (long long)m, n, C);
+  ASV_HIP_CHECK(hipGetLastError());
+  return ASV_OK;
+}
+#endif
 }  // namespace asv
 
 using namespace asv;
@@ -486,6 +510,43 @@ extern "C" int asv_two_cov_trials(const float *enroll, int n_enroll, const float
   hipLaunchKernelGGL(two_cov_trials_kernel, dim3((n_trials + 3) / 4), dim3(256), 0, s, enroll, test, dim, d_el.as<double>(), d_tl.as<double>(), d_eg.as<double>(),
                      d_tg.as<double>(), d_c.as<double>(), ei, ti, n_trials, scores);
   ASV_HIP_CHECK(hipGetLastError());
+  ASV_HIP_CHECK(hipStreamSynchronize(s));            // the scratch products are freed on return
+  return ASV_OK;
+}
+
+
+// All-pairs two-covariance scores: see include/asv_amd.h.  With EL = E Lambda, TL = T Lambda, EG = E Gamma, TG = T Gamma (the products
+// asv_two_cov_trials makes) the score of (i, j) is <[EL_i | e_i], [t_j | TL_j]> + (<EG_i, e_i> + <e_i, c>) + (<TG_j, t_j> + <t_j, c>).
+extern "C" int asv_two_cov_matrix(const float *enroll, int n_enroll, const float *test, int n_test, int dim, const double *gamma, const double *lambda,
+                                  const double *c, double *scores, void *stream) {
+  ASV_REQUIRE(enroll && test && gamma && lambda && c && scores, "asv_two_cov_matrix: null argument");
+  ASV_REQUIRE(n_enroll >= 1 && n_test >= 1 && dim >= 1 && dim <= 4096, "asv_two_cov_matrix: bad sizes (%d enrolment, %d test vectors, dim %d; 1 .. 4096)", n_enroll,
+              n_test, dim);
+  ASV_ON_OWNER(enroll, "asv_two_cov_matrix");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const size_t DD = (size_t)dim * dim;
+  const int kp = round_up(2 * dim, kScoreMatrixKChunk);
+  DevBuf d_g, d_l, d_c, d_el, d_tl, d_eg, d_tg, d_a, d_b, d_row, d_col, partials;
+  size_t partial_cap = 0;
+  int rc;
+  if ((rc = d_g.alloc(DD * 8)) || (rc = d_l.alloc(DD * 8)) || (rc = d_c.alloc((size_t)dim * 8)) || (rc = d_el.alloc((size_t)n_enroll * dim * 8)) ||
+      (rc = d_eg.alloc((size_t)n_enroll * dim * 8)) || (rc = d_tl.alloc((size_t)n_test * dim * 8)) || (rc = d_tg.alloc((size_t)n_test * dim * 8)) ||
+      (rc = d_a.alloc((size_t)n_enroll * kp * 8)) || (rc = d_b.alloc((size_t)n_test * kp * 8)) || (rc = d_row.alloc((size_t)n_enroll * 8)) ||
+      (rc = d_col.alloc((size_t)n_test * 8))) return rc;
+  ASV_HIP_CHECK(hipMemcpyAsync(d_g.p, gamma, DD * 8, hipMemcpyHostToDevice, s));
+  ASV_HIP_CHECK(hipMemcpyAsync(d_l.p, lambda, DD * 8, hipMemcpyHostToDevice, s));
+  ASV_HIP_CHECK(hipMemcpyAsync(d_c.p, c, (size_t)dim * 8, hipMemcpyHostToDevice, s));
+  auto rows_times = [&](const float *v, int n, const DevBuf &m, DevBuf &out) {
+    Gemm64Params g; memset(&g, 0, sizeof(g));
+    g.a = v; g.sa_i = dim; g.sa_k = 1; g.b = m.p; g.sb_k = dim; g.sb_j = 1; g.c = out.as<double>();
+    g.m = n; g.n = dim; g.k = dim; g.ldc = dim; g.alpha = 1.0; g.beta = 0.0;
+    return gemm64<float, double>(g, 1, partials, partial_cap, s);
+  };
+  if ((rc = rows_times(enroll, n_enroll, d_l, d_el)) || (rc = rows_times(test, n_test, d_l, d_tl)) || (rc = rows_times(enroll, n_enroll, d_g, d_eg)) ||
+      (rc = rows_times(test, n_test, d_g, d_tg))) return rc;
+  if ((rc = launch_two_cov_prep(enroll, n_enroll, dim, d_el.as<double>(), d_eg.as<double>(), d_c.as<double>(), true, d_a.as<double>(), kp, d_row.as<double>(), s)) ||
+      (rc = launch_two_cov_prep(test, n_test, dim, d_tl.as<double>(), d_tg.as<double>(), d_c.as<double>(), false, d_b.as<double>(), kp, d_col.as<double>(), s)) ||
+      (rc = launch_score_matrix<double>(d_a.as<double>(), n_enroll, d_b.as<double>(), n_test, kp, d_row.as<double>(), d_col.as<double>(), scores, s))) return rc;
   ASV_HIP_CHECK(hipStreamSynchronize(s));            // the scratch products are freed on return
   return ASV_OK;
 }

@@ -12,6 +12,9 @@
 #include <vector>
 
 #include "device_utils.h"
+#ifdef ASV_WITH_ABLATION
+#include <stdlib.h>      // getenv: the developer build's route switch of asv_plda_llr_matrix
+#endif
 
 namespace asv {
 namespace {
@@ -61,11 +64,6 @@ __global__ __launch_bounds__(256) void group_mean_kernel(const float *x, int n, 
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
   return v;
@@ -643,6 +641,34 @@ int asv_plda_llr_trials(const float *enroll, const float *test, int dim, const f
                      n_trials, scores);
   ASV_HIP_CHECK(hipGetLastError());
   return ASV_OK;
+}
+
+int asv_plda_llr_matrix(const float *enroll, int n_enroll, const float *test, int n_test, int dim, const float *psi, const int32_t *enroll_n, float *scores,
+                        void *stream) {
+  ASV_REQUIRE(enroll && test && psi && scores, "asv_plda_llr_matrix: null argument");
+  ASV_REQUIRE(n_enroll >= 1 && n_test >= 1 && dim >= 1 && dim <= 4096, "asv_plda_llr_matrix: bad sizes (%d enrolment, %d test vectors, dim %d; 1 .. 4096)", n_enroll,
+              n_test, dim);
+  ASV_ENTER(enroll);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int kp = round_up(2 * dim, kScoreMatrixKChunk);
+  const size_t a_bytes = round_up64((int64_t)n_enroll * kp * 8, 256), b_bytes = round_up64((int64_t)n_test * kp * 8, 256), r_bytes = round_up64((int64_t)n_enroll * 8, 256);
+  size_t extra = 0;
+#ifdef ASV_WITH_ABLATION
+  const char *route = getenv("ASV_AMD_SCORE_MATRIX");
+  const bool valu = route && !strcmp(route, "valu");
+  if (valu) extra = (size_t)n_enroll * n_test * 8;
+#endif
+  Workspace g_ws;
+  void *ws = nullptr;
+  int rc = g_ws.get(a_bytes + b_bytes + r_bytes + extra, s, &ws);
+  if (rc) return rc;
+  unsigned char *b = reinterpret_cast<unsigned char *>(ws);
+  double *A = reinterpret_cast<double *>(b), *B = reinterpret_cast<double *>(b + a_bytes), *row = reinterpret_cast<double *>(b + a_bytes + b_bytes);
+  if ((rc = launch_plda_llr_prep(enroll, n_enroll, test, n_test, dim, psi, enroll_n, A, B, kp, row, s))) return rc;
+#ifdef ASV_WITH_ABLATION
+  if (valu) return score_matrix_valu_f32(A, n_enroll, B, n_test, kp, row, reinterpret_cast<double *>(b + a_bytes + b_bytes + r_bytes), scores, s);
+#endif
+  return launch_score_matrix<float>(A, n_enroll, B, n_test, kp, row, nullptr, scores, s);
 }
 
 int asv_group_mean(const float *x, int n, int dim, const int32_t *order, const int32_t *offsets, int n_groups, float *means, int32_t *counts, void *stream) {

@@ -187,6 +187,7 @@ SYMBOLS = [
     "asv_tdnn_forward", "asv_stats_pool_forward",
     "asv_length_norm", "asv_mean_vec", "asv_dot_score_matrix", "asv_dot_score_trials",
     "asv_plda_transform", "asv_plda_llr_trials", "asv_eer", "asv_det_curve", "asv_min_dcf", "asv_cavg", "asv_score_norm", "asv_group_mean", "asv_two_cov_trials",
+    "asv_plda_llr_matrix", "asv_two_cov_matrix",
     "asv_plda_train", "asv_scatter_f64", "asv_class_scatter_f64",
     "asv_fbank_num_frames", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
     "asv_ingest_frames",
@@ -259,6 +260,8 @@ def lib():
     L.asv_cavg.argtypes = [vp, vp, vp, ci, ci, ci, C.c_double, c_double_p, c_double_p, vp]
     L.asv_group_mean.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp]
     L.asv_two_cov_trials.argtypes = [vp, ci, vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, ci, vp, vp]
+    L.asv_plda_llr_matrix.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
+    L.asv_two_cov_matrix.argtypes = [vp, ci, vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]
     L.asv_score_norm.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp]
     L.asv_plda_train.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), ci, ci,
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), vp]

@@ -362,6 +362,27 @@ class Plda(object):
                    "asv_plda_llr_trials")
         return out
 
+    def llr_matrix(self, enroll_t, test_t, enroll_num_utts=None):
+        """plda_base.py:109-136 for every (enrolment, test) pair of already-transformed vectors: device f32 [E, T]
+        (asv_plda_llr_matrix - per-vector terms once, then one float64 matrix product on the matrix cores).  What score_normalize
+        takes as its cohort matrices: llr_matrix(enroll, cohort, num_utts) and llr_matrix(test, cohort)."""
+        import torch
+        e, t = _dev(enroll_t, torch.float32), _dev(test_t, torch.float32)
+        dev = e.device
+        if e.dim() != 2 or t.dim() != 2 or e.shape[1] != self.dim or t.shape[1] != self.dim:
+            raise ValueError("llr_matrix: %d-dimensional model, vectors of shape %s / %s" % (self.dim, tuple(e.shape), tuple(t.shape)))
+        if e.shape[0] < 1 or t.shape[0] < 1:
+            raise ValueError("llr_matrix: %d enrolment and %d test vectors - an empty set has no score matrix" % (e.shape[0], t.shape[0]))
+        t = t.to(dev)
+        psi = _dev(self.psi.astype(np.float32), device=dev)
+        en = _dev(enroll_num_utts, torch.int32, dev) if enroll_num_utts is not None else None
+        if en is not None and (en.dim() != 1 or en.shape[0] != e.shape[0]):
+            raise ValueError("llr_matrix: %d enrolment vectors but %s num_utts entries" % (e.shape[0], tuple(en.shape)))
+        out = torch.empty((e.shape[0], t.shape[0]), dtype=torch.float32, device=dev)
+        capi.check(capi.lib().asv_plda_llr_matrix(_ptr(e), e.shape[0], _ptr(t), t.shape[0], self.dim, _ptr(psi), _ptr(en), _ptr(out), _stream(e)),
+                   "asv_plda_llr_matrix")
+        return out
+
 
 class TwoCovPlda(object):
     """Two-covariance PLDA scorer of score/pyplda/gaussian-plda-scoring.py: Gamma / Lambda / c from (mean, within, between)
@@ -400,6 +421,35 @@ class TwoCovPlda(object):
             capi.check(capi.lib().asv_two_cov_trials(_ptr(e), e.shape[0], _ptr(t), t.shape[0], self.dim, dp(self.gamma), dp(self.lam), dp(self.c),
                                                      _ptr(ei), _ptr(ti), ei.shape[0], _ptr(out), _stream(e)), "asv_two_cov_trials")
         return out
+
+    def score_matrix(self, enroll, test):
+        """The score of every (enrolment, test) pair: float64 device tensor [E, T] (asv_two_cov_matrix)."""
+        import torch
+        e, t = _dev(enroll, torch.float32), _dev(test, torch.float32)
+        if e.dim() != 2 or t.dim() != 2 or e.shape[1] != self.dim or t.shape[1] != self.dim:
+            raise ValueError("two_cov: %d-dimensional model, vectors of shape %s / %s" % (self.dim, tuple(e.shape), tuple(t.shape)))
+        if e.shape[0] < 1 or t.shape[0] < 1:
+            raise ValueError("two_cov: %d enrolment and %d test vectors - an empty set has no score matrix" % (e.shape[0], t.shape[0]))
+        t = t.to(e.device)
+        out = torch.empty((e.shape[0], t.shape[0]), dtype=torch.float64, device=e.device)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        with torch.cuda.device(e.device):
+            capi.check(capi.lib().asv_two_cov_matrix(_ptr(e), e.shape[0], _ptr(t), t.shape[0], self.dim, dp(self.gamma), dp(self.lam), dp(self.c),
+                                                     _ptr(out), _stream(e)), "asv_two_cov_matrix")
+        return out
+
+
+def plda_asnorm_trials(plda, enroll, test, cohort, enroll_idx, test_idx, enroll_num_utts=None, top_n=300, cross_select=False, normalize_length=True,
+                       simple_length_norm=False):
+    """The PLDA twin of cosine_asnorm_trials: transform the three sets (enrol with its num_utts, test and cohort with 1), LLR for
+    the trials and for enrol x cohort / test x cohort - the cohort always on the test side, the test vectors taking the enrolment
+    role with one utterance each - then S-norm / AS-norm, all on the device.  The reference gets there by scoring all-pairs trial
+    files with ivector-plda-scoring (score/score.sh:99-121) and handing them to score/ScoreNormalization.py."""
+    kw = dict(normalize_length=normalize_length, simple_length_norm=simple_length_norm)
+    e = plda.transform_vectors(enroll, enroll_num_utts, **kw)
+    t, c = plda.transform_vectors(test, None, **kw), plda.transform_vectors(cohort, None, **kw)
+    raw = plda.llr_trials(e, t, enroll_idx, test_idx, enroll_num_utts)
+    return score_normalize(raw, plda.llr_matrix(e, c, enroll_num_utts), plda.llr_matrix(t, c), enroll_idx, test_idx, top_n=top_n, cross_select=cross_select)
 
 
 def second_moments(vectors):

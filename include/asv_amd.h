@@ -416,6 +416,22 @@ int asv_group_mean(const float *x, int n, int dim, const int32_t *order, const i
 int asv_two_cov_trials(const float *enroll, int n_enroll, const float *test, int n_test, int dim, const double *gamma,
                        const double *lambda, const double *c, const int32_t *ei, const int32_t *ti, int n_trials,
                        double *scores, void *stream);
+/* All-pairs PLDA score matrices: what the reference gets by scoring an all-pairs trial file and what asv_score_norm takes as its
+ * enrol x cohort / test x cohort inputs (score/ScoreNormalization.py:70-179 reads them whichever scorer wrote them).
+ *   asv_plda_llr_matrix: scores[i][j] = the log-likelihood ratio of plda_base.py:109-136 of enrolment vector i (enroll_n[i]
+ *     utterances behind it; NULL = 1 each) and test vector j, device f32 dense [n_enroll][n_test].  Everything that depends on one
+ *     side only (the logs and divisions of lines 116-118, 129-131) is evaluated once per vector in float64; the pair loop is one
+ *     float64 matrix product of K = 2 dim on the matrix cores (v_mfma_f64_16x16x4_f64) plus a per-row term, rounded to f32 once.
+ *     Pointers as in asv_plda_llr_trials: vectors, psi, enroll_n, scores on the device.  dim <= 4096.  Asynchronous on `stream`; the
+ *     operands live in stream-ordered scratch.  Summation order differs from asv_plda_llr_trials: the last f32 bit may differ.
+ *   asv_two_cov_matrix: scores[i][j] = the two-covariance score of gaussian-plda-scoring.py:23-29 (see asv_two_cov_trials) of
+ *     enrolment vector i and test vector j, device float64 dense [n_enroll][n_test]; gamma / lambda / c: HOST float64 as in
+ *     asv_two_cov_trials.  Four f64 GEMMs (vectors x G, vectors x L) and one f64 matrix product of K = 2 dim.  dim <= 4096.
+ *     Like asv_two_cov_trials it SYNCHRONISES `stream` before it returns (its scratch products are freed on return). */
+int asv_plda_llr_matrix(const float *enroll, int n_enroll, const float *test, int n_test, int dim, const float *psi,
+                        const int32_t *enroll_n, float *scores, void *stream);
+int asv_two_cov_matrix(const float *enroll, int n_enroll, const float *test, int n_test, int dim, const double *gamma,
+                       const double *lambda, const double *c, double *scores, void *stream);
 /* Equal error rate (score/computeEER-like-Bosaris.py:50-91 semantics) of device scores with
  * device int32 labels (1 target / 0 non-target).  eer_percent / threshold are host outputs;
  * the call synchronises `stream`. */
