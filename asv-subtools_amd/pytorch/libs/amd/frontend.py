@@ -268,3 +268,52 @@ def ingest(feats, frame_off, voiced=None, cmn_window=0, min_window=100, center=T
                                                 int(bool(norm_vars)), C.c_void_p(out.data_ptr()),
                                                 C.c_void_p(torch.cuda.current_stream(feats.device).cuda_stream)), "asv_ingest_frames")
     return out[:rows], kept_off
+
+
+COMPRESSED_FORMATS = {"CM ": 1, "CM2": 2, "CM3": 3}          # Kaldi's token -> the format byte of asv_decode_compressed
+
+
+def compressed_body_bytes(fmt, rows, cols):
+    """Bytes of the body of a Kaldi compressed matrix (from its 16-byte global header to its end); numbers or arrays."""
+    fmt, data = np.asarray(fmt), np.asarray(rows, dtype=np.int64) * np.asarray(cols, dtype=np.int64)
+    return 16 + np.where(fmt == 1, 8 * np.asarray(cols, dtype=np.int64) + data, np.where(fmt == 2, 2 * data, data))
+
+
+def decode_compressed(bytes_dev, byte_off, frame_off, formats, dim, out=None):
+    """The bodies of Kaldi compressed matrices ('CM ' / 'CM2' / 'CM3', each from its 16-byte global header, as they lie on disk) in a
+    uint8 CUDA tensor -> packed float32 rows, in one launch on the current stream (asv_decode_compressed); bit for bit what
+    libs.support.kaldi_io.read_mat gives for the same bytes.  byte_off int64 [n]: start of each body in bytes_dev, multiples of 16;
+    frame_off int64 [n + 1] from 0; formats uint8 [n] (COMPRESSED_FORMATS).  The rows and columns used are those of frame_off and dim -
+    whoever filled the bytes has compared them with the headers (ScpBatchLoader.load_compressed does); here every body only has to lie
+    inside bytes_dev.  Returns `out[:frame_off[-1]]` ([rows, dim] f32 CUDA tensor; allocated when not given)."""
+    import torch
+    byte_off, frame_off = _off(byte_off), _off(frame_off)
+    formats = np.ascontiguousarray(formats, dtype=np.uint8)
+    n = len(frame_off) - 1
+    dim = int(dim)
+    if bytes_dev.dim() != 1 or bytes_dev.dtype != torch.uint8 or not bytes_dev.is_cuda or not bytes_dev.is_contiguous():
+        raise ValueError("decode_compressed: bytes_dev must be a contiguous 1-D uint8 CUDA tensor")
+    if n < 1 or len(byte_off) != n or len(formats) != n or dim < 1:
+        raise ValueError("decode_compressed: one byte offset and one format per utterance, frame_off with one entry more, dim >= 1")
+    if bytes_dev.data_ptr() % 16:
+        raise ValueError("decode_compressed: bytes_dev must start at a 16-byte boundary")
+    rows_of = np.diff(frame_off)
+    if int(frame_off[0]) != 0 or (rows_of < 0).any():
+        raise ValueError("decode_compressed: frame_off must start at 0 and not decrease")
+    if not np.isin(formats, (1, 2, 3)).all():
+        raise ValueError("decode_compressed: formats are 1 ('CM '), 2 ('CM2') or 3 ('CM3')")
+    ends = byte_off + compressed_body_bytes(formats, rows_of, dim)
+    if (byte_off < 0).any() or (ends > bytes_dev.shape[0]).any():
+        raise ValueError("decode_compressed: a body reaches beyond the %d bytes handed over" % bytes_dev.shape[0])
+    rows = int(frame_off[-1])
+    if out is None:
+        out = torch.empty((rows, dim), dtype=torch.float32, device=bytes_dev.device)
+    elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != dim or out.shape[0] < rows:
+        raise ValueError("decode_compressed: out must be a contiguous f32 CUDA tensor of at least [%d, %d]" % (rows, dim))
+    if rows == 0:
+        return out[:0]
+    with torch.cuda.device(bytes_dev.device):
+        capi.check(capi.lib().asv_decode_compressed(C.c_void_p(bytes_dev.data_ptr()), _i64p(byte_off), _i64p(frame_off),
+                                                    formats.ctypes.data_as(C.POINTER(C.c_ubyte)), n, dim, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(torch.cuda.current_stream(bytes_dev.device).cuda_stream)), "asv_decode_compressed")
+    return out[:rows]

@@ -43,10 +43,14 @@ class DeviceSets(object):
     a page-locked flag buffer with its device twin, and submit(k, offsets, frames, voiced) puts the fused CMN + selection launch between the
     H2D copies and the extraction, on the same stream (no synchronisation: the kept counts come from the host flags).  The engine sees
     the compacted rows and offsets; utterances that keep no frame are left out (finish() returns one vector per utterance that kept some).
+    compressed=True: the reader may hand over Kaldi COMPRESSED matrices as they lie on disk - every set also holds a page-locked uint8
+    staging buffer (byte_buffer(k), filled by ScpBatchLoader.load_compressed) with its device twin, and submit_compressed() copies the
+    bytes used and decodes them on the engine's stream (asv_decode_compressed) into the rows submit() would have copied, then goes on as
+    submit() does.  A quarter of the H2D bytes, and no decode on the host.
     ASV_AMD_PIPELINE_ENGINES=1 keeps one engine on one stream (device-resident rate of two: +5 % x-vector, +9 % ECAPA, +19 %
     ResNet34-SE, profiles/r3h_streams.txt)."""
 
-    def __init__(self, model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", n_engines=2, warm=True, ingest=None):
+    def __init__(self, model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", n_engines=2, warm=True, ingest=None, compressed=False):
         import torch
         assert results in ("host", "device")
         self.torch = torch
@@ -86,6 +90,14 @@ class DeviceSets(object):
                 self.host_flags = [torch.zeros(batch_frames, dtype=torch.uint8).pin_memory() for _ in range(n_sets)]
                 self.flags_np = [t.numpy() for t in self.host_flags]
                 self.dev_flags = [torch.empty(batch_frames, dtype=torch.uint8, device=dev) for _ in range(n_sets)]
+        self.host_bytes = self.bytes_np = self.dev_bytes = None                          # compressed=False: nothing is allocated, nothing is launched
+        if compressed:
+            # the worst case of a full batch: 'CM2' takes 2 bytes per value, every body its global header, 'CM ' its column headers, and
+            # each starts at a 16-byte boundary
+            size = 2 * batch_frames * dim + batch_utts * (32 + 8 * dim)
+            self.host_bytes = [torch.zeros(size, dtype=torch.uint8).pin_memory() for _ in range(n_sets)]
+            self.bytes_np = [t.numpy() for t in self.host_bytes]
+            self.dev_bytes = [torch.zeros(size, dtype=torch.uint8, device=dev) for _ in range(n_sets)]
         if results == "host":
             self.dev_out = [torch.empty((batch_utts, self.embed_dim), dtype=torch.float32, device=dev) for _ in range(n_sets)]
             self.host_out = [torch.empty((batch_utts, self.embed_dim), dtype=torch.float32).pin_memory() for _ in range(n_sets)]
@@ -105,6 +117,9 @@ class DeviceSets(object):
                         eng.extract_device(self.dev_in[0][:int(offs[-1])], offs, max_chunk=self.max_chunk)
                         if ingest is not None:         # (the ingest kernel's code object, and this thread's offset staging in the library)
                             self._ingest(self.dev_in[0][:int(offs[-1])], offs.astype(np.int64), None, None, self.dev_raw[0])
+                        if compressed:                 # (the decode kernel's code object and its offset staging; a one-row 'CM3' body of zeros)
+                            self._decode(self.dev_bytes[0], np.zeros(1, dtype=np.int64), np.array([0, 1], dtype=np.int64), np.full(1, 3, dtype=np.uint8),
+                                         (self.dev_in if ingest is None else self.dev_raw)[0])
                         if self.watch:
                             eng.status_async(self.status_host[0])
                 for st in self.streams:
@@ -120,6 +135,14 @@ class DeviceSets(object):
         """[batch_frames] uint8 numpy view of set k's page-locked flag buffer (ingest with flags): the reader fills it next to host_buffer(k)."""
         return self.flags_np[k]
 
+    def byte_buffer(self, k):
+        """uint8 numpy view of set k's page-locked staging buffer for compressed bodies (compressed=True)."""
+        return self.bytes_np[k]
+
+    def _decode(self, dev_bytes, byte_off, frame_off, formats, out):
+        from . import frontend
+        return frontend.decode_compressed(dev_bytes, byte_off, frame_off, formats, out.shape[1], out=out)
+
     def _ingest(self, raw, raw_off, dev_flags, kept_off, out):
         from . import frontend
         o = self.ingest
@@ -129,6 +152,24 @@ class DeviceSets(object):
     def submit(self, k, offsets, frames, voiced=None, kept_off=None):
         """`voiced` (ingest with flags): one uint8 flag per raw row - flag_buffer(k)[:frames] as the reader filled it, or an array of its
         own; `kept_off`: its per-utterance running sum where the caller has it already (frontend.kept_offsets)."""
+        return self._submit(k, offsets, frames, None, voiced, kept_off)
+
+    def submit_compressed(self, k, byte_off, frame_off, formats, used_bytes, voiced=None, kept_off=None):
+        """The batch lies in byte_buffer(k)[:used_bytes] as compressed bodies (what ScpBatchLoader.load_compressed returned): the bytes
+        are copied, decoded on the engine's stream into the rows submit() copies, and everything behind that is submit()'s."""
+        if self.dev_bytes is None:
+            raise ValueError("these buffer sets were made without compressed=True")
+        frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        rows, used_bytes = int(frame_off[-1]), int(used_bytes)
+        if rows > self.dev_in[k].shape[0] or not 0 < used_bytes <= self.dev_bytes[k].shape[0]:
+            raise ValueError("a compressed batch of %d rows in %d bytes does not fit the buffer set (%d rows, %d bytes)" % (
+                rows, used_bytes, self.dev_in[k].shape[0], self.dev_bytes[k].shape[0]))
+        return self._submit(k, frame_off.astype(np.int32), rows, (np.ascontiguousarray(byte_off, dtype=np.int64), frame_off, formats, used_bytes), voiced, kept_off)
+
+    def _submit(self, k, offsets, frames, packed, voiced, kept_off):
+        """submit() (`packed` None: `frames` rows of host_buffer(k), or an array of its own) and submit_compressed() (`packed` = (byte_off,
+        frame_off, formats, used_bytes) of byte_buffer(k)): they differ in what is copied to the device and in the decode launch behind
+        the copy - the flags, the ingest, the extraction, the result copy and the status word are the same code."""
         torch = self.torch
         assert self.pending[k] is None, "set %d still holds a batch: finish() it first" % k
         n = len(offsets) - 1
@@ -168,8 +209,11 @@ class DeviceSets(object):
         import time
         t = [time.perf_counter()]
         with torch.cuda.device(self.dev), torch.cuda.stream(self.streams[e]):
-            own = isinstance(frames, np.ndarray)
-            if own:                                      # one utterance longer than a whole batch buffer: a pageable copy of its own
+            own = packed is None and isinstance(frames, np.ndarray)
+            if packed is not None:                       # compressed bodies: only the bytes used travel; the rows are decoded behind the copy
+                self.dev_bytes[k][:packed[3]].copy_(self.host_bytes[k][:packed[3]], non_blocking=True)
+                feats = (self.dev_in if self.ingest is None else self.dev_raw)[k][:frames]
+            elif own:                                    # one utterance longer than a whole batch buffer: a pageable copy of its own
                 feats = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.float32)).to(self.dev)
             else:
                 feats = (self.dev_in if self.ingest is None else self.dev_raw)[k][:frames]
@@ -186,6 +230,9 @@ class DeviceSets(object):
                     flags.copy_(self.host_flags[k][:rows], non_blocking=True)
             self.h2d[k].record()
             t.append(time.perf_counter())
+            if packed is not None:
+                self._decode(self.dev_bytes[k], packed[0], packed[1], packed[2], feats)
+                t.append(time.perf_counter())
             if self.ingest is not None:                  # raw rows -> normalised kept rows, compacted: what the engine (and a range re-run) reads
                 feats = self._ingest(feats, raw_off, flags, kept_off, None if own else self.dev_in[k])
                 t.append(time.perf_counter())
@@ -199,7 +246,8 @@ class DeviceSets(object):
                 self.engines[e].status_async(self.status_host[k])
             self.done[k].record()
             t.append(time.perf_counter())
-        for i, name in enumerate(("h2d", "extract", "d2h") if self.ingest is None else ("h2d", "ingest", "extract", "d2h")):
+        pieces = ("h2d",) + (("decode",) if packed is not None else ()) + (("ingest",) if self.ingest is not None else ()) + ("extract", "d2h")
+        for i, name in enumerate(pieces):
             self.submit_seconds[name] = self.submit_seconds.get(name, 0.0) + t[i + 1] - t[i]
         self.submitted += 1
         self.pending[k] = (feats, np.array(offsets, dtype=np.int32), out, n, e, self.submitted)

@@ -22,6 +22,11 @@ launch per batch between the H2D copy and the extraction (libs.amd.pipeline.Devi
 feats-rspecifier can be the raw `scp:feats.scp`.  As select-voiced-frames does, an utterance without a VAD entry, with a VAD
 vector of another length than its matrix, or without a voiced frame is skipped with a WARNING line on stderr.
 
+Compressed features: Kaldi's make_fbank.sh / make_mfcc.sh write feats.scp as compressed matrices by default (`\0BCM `; also `CM2`, `CM3`).  With `scp:`
+input (not --sharded) the bodies of such 'file:offset' entries are read as they lie on disk - one byte per value - and decoded on the device
+(asv_decode_compressed) in front of the ingest / the extraction: the same float32 rows, bit for bit, as the host reader's.  Range-specified entries,
+pipes, text and float64 matrices go through the host reader as before; ASV_AMD_DEVICE_DECODE=0 sends everything there.
+
 Multi-GPU (--sharded true, launched as `python -m torch.distributed.run --nproc-per-node N ... extract_embeddings.py ...`, one
 process per GPU): replaces the reference's `nj` jobs over a length-balanced split of feats.scp and the final
 `cat xvector.JOB.scp` (pipeline/extract_xvectors_for_pytorch.sh:90-100,125-151; splitDataByLength.sh:44-80).  Every rank reads
@@ -221,7 +226,7 @@ class VadTable(object):
 
 def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=False, reader=None, ingest=None, vad=None):
     """feature ark stream -> embedding ark stream, pipelined in three stages over two buffer sets:
-      reader thread   next packed batch -> pinned host buffer   (kaldi_io.IndexedArkReader for ark files - native index + batched reads -,
+      reader thread   next packed batch -> pinned host buffer (the bodies of compressed scp entries: as they are -> pinned byte buffer)   (kaldi_io.IndexedArkReader for ark files - native index + batched reads -,
                       kaldi_io.PackedArkReader for pipes: block reads, no per-utterance arrays; ScpGroupReader for `scp:` input)
       device          async H2D, asv_net_extract, async D2H into a pinned result buffer + the range status word   (libs.amd.pipeline.DeviceSets:
                       each buffer set has its own engine - same weights, own activation arena - on its own HIP stream)
@@ -252,7 +257,11 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
     # 128 / 256 rows: a group is cut so that its ROWS fit --batch-frames (65 536 = 256 tiles of 256 rows: 321 utterances of 200 frames
     # fill whole rounds of tiles on the 256 CUs; 327 - the frames alone - were 2.04 rounds of 128-row tiles, i.e. three)
     reader.row_pad = 4
-    sets = DeviceSets(model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", ingest=ingest)
+    # Kaldi's feature scripts write COMPRESSED matrices by default: where the scp table holds such entries their bodies are read as they
+    # lie on disk into a page-locked byte buffer and decoded on the device (a quarter of the bytes read and copied, no numpy decode per
+    # utterance); ASV_AMD_DEVICE_DECODE=0 keeps the host decode (A/B runs, escape hatch)
+    compressed = os.environ.get("ASV_AMD_DEVICE_DECODE", "1") != "0" and hasattr(reader, "has_compressed") and reader.has_compressed()
+    sets = DeviceSets(model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", ingest=ingest, compressed=compressed)
     free_sets, batches = queue.Queue(), queue.Queue()
     for k in range(sets.n_sets):
         free_sets.put(k)
@@ -261,7 +270,10 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
         try:
             while True:
                 k = free_sets.get()
-                keys, offsets, frames = reader.read_group(sets.host_buffer(k), batch_utts)
+                if compressed:
+                    keys, offsets, frames = reader.read_group(sets.host_buffer(k), batch_utts, byte_buffer=sets.byte_buffer(k))
+                else:
+                    keys, offsets, frames = reader.read_group(sets.host_buffer(k), batch_utts)
                 staged.put((k, keys, offsets, frames, None))
                 if not keys:
                     return
@@ -280,7 +292,8 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
                 voiced = None
                 if keys:
                     a = clock()
-                    flags = np.zeros(frames.shape[0], dtype=np.uint8) if isinstance(frames, np.ndarray) else sets.flag_buffer(k)[:frames]
+                    rows = frames.frames if isinstance(frames, CompressedGroup) else frames
+                    flags = np.zeros(rows.shape[0], dtype=np.uint8) if isinstance(rows, np.ndarray) else sets.flag_buffer(k)[:rows]
                     voiced = (flags,) + vad.flags_for(keys, offsets, flags)
                     spent["vad"] += clock() - a
                 batches.put((k, keys, offsets, frames, voiced))
@@ -328,8 +341,12 @@ def extract_stream(model, r, w, batch_frames, batch_utts, max_chunk, verbose=Fal
         k, keys, offsets, frames, voiced = item
         if not keys:
             break
+        flags = kept_off = None
         if voiced is not None:
             flags, keys, kept_off = voiced            # (the keys that keep a frame: one vector each)
+        if isinstance(frames, CompressedGroup):       # compressed bodies in the set's byte buffer: decoded on the device
+            sets.submit_compressed(k, frames.byte_off, frames.frame_off, frames.formats, frames.used_bytes, voiced=flags, kept_off=kept_off)
+        elif voiced is not None:
             sets.submit(k, offsets, frames, voiced=flags, kept_off=kept_off)
         else:
             sets.submit(k, offsets, frames)
@@ -528,7 +545,10 @@ class ScpBatchLoader(object):
     (0.65 GB/s) per rank against 56 k for the sequential stream reader and ~950 k the device extracts.  Here an uncompressed float32
     entry 'file.ark:offset' (what copy-feats / the reference's make_features write) costs one 15-byte header pread and one read of its
     payload straight into its rows of the batch buffer; everything else - float64, compressed, text matrices, range specifiers,
-    pipes - goes through read_matrix and is copied in.  Two buffers alternate: libs.amd.shard.extract_sharded fetches batch k + 1
+    pipes - goes through read_matrix and is copied in.  A COMPRESSED 'file.ark:offset' entry ('CM ' / 'CM2' / 'CM3': what Kaldi's
+    make_fbank.sh / make_mfcc.sh write) is a second kind of direct entry: its format, body offset, rows and columns are in the header
+    table too (lengths() and shape() answer from it), and load_compressed() reads the bodies of a batch as they are into a byte
+    buffer for the device decode - fill() / load_batch() still decode such an entry on the host.  Two buffers alternate: libs.amd.shard.extract_sharded fetches batch k + 1
     while batch k is on the device.  The buffers are the loader's own arrays, or the CALLER's (`buffers`: e.g. the page-locked
     input buffers of libs.amd.pipeline.DeviceSets, so that the H2D copy starts from where the file was read to; `before_fill(turn)`
     is then called before buffer `turn` is overwritten - the caller waits for its copy out of it there).  `loader(i)` (one
@@ -551,6 +571,8 @@ class ScpBatchLoader(object):
         self._fds = collections.OrderedDict()            # path -> descriptor, least recently used first
         self._heads = {}
         self._table = None                               # index_all(): (plain, file id, payload offset, rows, cols) arrays + the file list
+        self._ctable = None                              # index_all(): (format 0 / 1 / 2 / 3, body offset, rows, cols) arrays of the COMPRESSED direct entries
+        self._cheads = {}
         self._bufs = list(buffers) if buffers is not None else [None, None]
         self._own = buffers is None
         self._before_fill = before_fill
@@ -603,6 +625,84 @@ class ScpBatchLoader(object):
                     h = (path, off + 15, struct.unpack_from("<i", head, 6)[0], struct.unpack_from("<i", head, 11)[0])
         self._heads[i] = h
         return h
+
+    @staticmethod
+    def _parse_compressed(heads):
+        """heads uint8 [m, 22+]: the first bytes of m entries -> (format uint8 [m]: 1 'CM ', 2 'CM2', 3 'CM3', 0 none of them; token length,
+        rows, cols of the 16-byte global header {float min, float range, int32 rows, int32 cols} behind the token)."""
+        cm = (heads[:, 0] == 0) & (heads[:, 1] == ord("B")) & (heads[:, 2] == ord("C")) & (heads[:, 3] == ord("M"))
+        fmt = np.zeros(len(heads), dtype=np.uint8)
+        fmt[cm & (heads[:, 4] == ord(" "))] = 1
+        fmt[cm & (heads[:, 4] == ord("2")) & (heads[:, 5] == ord(" "))] = 2
+        fmt[cm & (heads[:, 4] == ord("3")) & (heads[:, 5] == ord(" "))] = 3
+        token = np.where(fmt == 1, 5, 6).astype(np.int64)
+        at = token[:, None] + np.arange(8, 16, dtype=np.int64)[None]
+        counts = np.ascontiguousarray(np.take_along_axis(heads, at, axis=1)).view("<i4")
+        rows, cols = counts[:, 0].astype(np.int64), counts[:, 1].astype(np.int64)
+        fmt[(rows < 1) | (cols < 1)] = 0                     # (an empty or damaged matrix: the host reader deals with it)
+        return fmt, token, rows, cols
+
+    def _direct_compressed(self, i):
+        """(path, body offset, rows, cols, format) of entry i if it is a Kaldi compressed matrix ('CM ' = 1, 'CM2' = 2, 'CM3' = 3) behind a
+        'file:offset' entry without range specifier, else None.  The body starts at the 16-byte global header behind the token."""
+        if self._ctable is not None:
+            fmt, body, rows, cols = self._ctable
+            if not fmt[i]:
+                return None
+            return self._table[5][self._table[1][i]], int(body[i]), int(rows[i]), int(cols[i]), int(fmt[i])
+        h = self._cheads.get(i, 0)
+        if h != 0:
+            return h
+        rxfile = self.entries[i][1]
+        h = None
+        if not (rxfile.endswith("]") or rxfile.endswith("|") or ":" not in rxfile):
+            path, _, off = rxfile.rpartition(":")
+            if off.isdigit() and (path in self._fds or os.path.isfile(path)):
+                off = int(off)
+                head = os.pread(self._fd(path), 22, off)
+                if len(head) >= 21:
+                    fmt, token, rows, cols = self._parse_compressed(np.frombuffer(head.ljust(22, b"\0"), dtype=np.uint8)[None])
+                    if fmt[0] and len(head) >= int(token[0]) + 16:
+                        h = (path, off + int(token[0]), int(rows[0]), int(cols[0]), int(fmt[0]))
+        self._cheads[i] = h
+        return h
+
+    def compressed_format(self, i):
+        """1 / 2 / 3 when entry i is a compressed direct entry ('CM ' / 'CM2' / 'CM3': its body can be read as it is and decoded on the
+        device), else 0."""
+        h = self._direct_compressed(i)
+        return h[4] if h is not None else 0
+
+    def has_compressed(self):
+        """Does the table hold a compressed direct entry?  From the header table where there is one, else entry by entry up to the first."""
+        if self.index_all():
+            return bool(self._ctable[0].any())
+        return any(self._direct_compressed(i) is not None for i in range(len(self.entries)))
+
+    def _index_compressed(self, cand, heads15, lut, fid, off):
+        """Second header pass of index_all: the candidates whose first 15 bytes did not say `\\0BFM ` but `\\0BCM` get 22 bytes read (token +
+        global header; one native call) - the table of the compressed direct entries.  Per rank under --sharded: no collective."""
+        from libs.support import native_io
+        n = len(self.entries)
+        fmt_all, body, rows, cols = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        maybe = cand[(heads15[:, 0] == 0) & (heads15[:, 1] == ord("B")) & (heads15[:, 2] == ord("C")) & (heads15[:, 3] == ord("M"))]
+        if len(maybe):
+            heads = np.zeros((len(maybe), 32), dtype=np.uint8)
+            try:
+                native_io.pread_batch(lut[fid[maybe]], off[maybe], np.full(len(maybe), 22, dtype=np.int64), heads.ctypes.data,
+                                      np.arange(len(maybe), dtype=np.int64) * 32, threads=self.threads)
+            except OSError:
+                # (a 21-byte 'CM ' entry without a single column at the very end of a file: the same reads one by one, short ones allowed)
+                heads[:] = 0
+                for j, i in enumerate(maybe.tolist()):
+                    got = os.pread(int(lut[fid[i]]), 22, int(off[i]))
+                    if len(got) == 22 or (len(got) == 21 and got[4:5] == b" "):
+                        heads[j, :len(got)] = np.frombuffer(got, dtype=np.uint8)
+            fmt, token, r, c = self._parse_compressed(heads)
+            good = fmt > 0
+            at = maybe[good]
+            fmt_all[at], body[at], rows[at], cols[at] = fmt[good], off[at] + token[good], r[good], c[good]
+        self._ctable = (fmt_all, body, rows, cols)
 
     def index_all(self, ranks=None):
         """`ranks` = (rank, world, gather) under --sharded with more than one rank: the header pass is SHARED - every rank reads the
@@ -704,26 +804,28 @@ class ScpBatchLoader(object):
         good = cand[ok]
         plain[good], rows[good], cols[good] = True, rows_c[ok], cols_c[ok]
         self._table = (plain, fid, off + 15, rows, cols, files)
+        self._index_compressed(cand, heads, lut, fid, off)
         return True
 
     def lengths(self):
         """Frames of every entry, from the headers (what the length-balanced sharding needs when no utt2num_frames is given)."""
         if self.index_all():
             plain, _, _, rows, _, _ = self._table
-            out = rows.copy()
-            for i in np.nonzero(~plain)[0]:
+            fmt, _, c_rows, _ = self._ctable
+            out = np.where(fmt > 0, c_rows, rows)
+            for i in np.nonzero(~plain & (fmt == 0))[0]:
                 out[i] = matrix_rows(self.entries[i][1])
             return out
         out = np.empty(len(self.entries), dtype=np.int64)
         for i, (_, rx) in enumerate(self.entries):
-            h = self._direct(i)
+            h = self._direct(i) or self._direct_compressed(i)
             out[i] = h[2] if h is not None else matrix_rows(rx)
         return out
 
     def shape(self, i, slow=None):
-        """(rows, cols) of entry i: from its header if it is a plain float32 entry, else by decoding it (the matrix is kept in
-        `slow[i]` for the fill that follows)."""
-        h = self._direct(i)
+        """(rows, cols) of entry i: from its header if it is a plain float32 or a compressed direct entry, else by decoding it (the
+        matrix is kept in `slow[i]` for the fill that follows)."""
+        h = self._direct(i) or self._direct_compressed(i)
         if h is not None:
             return h[2], h[3]
         m = slow.get(i) if slow is not None else None
@@ -769,6 +871,72 @@ class ScpBatchLoader(object):
                 if r <= 0:
                     raise kaldi_io.BadInputFormat("scp entry %r: the archive ends inside the matrix" % (self.entries[indices[k]][1],))
                 got += r
+
+    def load_compressed(self, indices, byte_buffer):
+        """The BODIES of the compressed direct entries `indices` (each from its 16-byte global header, as it lies in the file), read in one
+        native call into the caller's uint8 `byte_buffer` (e.g. the page-locked staging buffer of libs.amd.pipeline.DeviceSets), every
+        body at a 16-byte boundary: what libs.amd.frontend.decode_compressed / DeviceSets.submit_compressed take.  Returns (byte_offsets
+        int64 [n], frame_offsets int64 [n + 1], formats uint8 [n], used_bytes).  The rows and columns the device will address come from
+        the header table; they are compared here with the header of every body as it was read, before anything is copied on."""
+        from libs.amd.frontend import compressed_body_bytes
+        from libs.support import native_io
+        if byte_buffer.dtype != np.uint8 or byte_buffer.ndim != 1 or not byte_buffer.flags["C_CONTIGUOUS"] or byte_buffer.ctypes.data % 16:
+            raise ValueError("load_compressed: byte_buffer must be a contiguous 1-D uint8 array that starts at a 16-byte boundary")
+        n = len(indices)
+        if self._ctable is not None:                         # the header table: a batch's arguments by array indexing, as _fill_table
+            idx = np.asarray(indices, dtype=np.int64)
+            t_fmt, t_body, t_rows, t_cols = self._ctable
+            formats, pos, rows, cols = t_fmt[idx], t_body[idx], t_rows[idx], t_cols[idx]
+            if not formats.all():
+                raise ValueError("scp entry %r is not a compressed direct entry" % (self.entries[int(idx[np.flatnonzero(formats == 0)[0]])][1],))
+            files, fid = self._table[5], self._table[1][idx]
+            paths = [files[j] for j in fid.tolist()]
+        else:
+            heads = [self._direct_compressed(int(i)) for i in indices]
+            for i, h in zip(indices, heads):
+                if h is None:
+                    raise ValueError("scp entry %r is not a compressed direct entry" % (self.entries[int(i)][1],))
+            pos = np.asarray([h[1] for h in heads], dtype=np.int64)
+            rows = np.asarray([h[2] for h in heads], dtype=np.int64)
+            cols = np.asarray([h[3] for h in heads], dtype=np.int64)
+            formats = np.asarray([h[4] for h in heads], dtype=np.uint8)
+            paths = [h[0] for h in heads]
+        if n and (cols != cols[0]).any():
+            raise ValueError("feature matrices of different widths in one batch: %s" % sorted(set(cols.tolist())))
+        size = compressed_body_bytes(formats, rows, cols).astype(np.int64) if n else np.zeros(0, dtype=np.int64)
+        byte_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum((size + 15) // 16 * 16, out=byte_off[1:])
+        used = int(byte_off[-1])
+        if used > byte_buffer.shape[0]:
+            raise ValueError("load_compressed: the bodies take %d bytes, the buffer holds %d" % (used, byte_buffer.shape[0]))
+        frame_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(rows, out=frame_off[1:])
+        byte_off = byte_off[:-1].copy()
+        used_paths = set(paths)
+        fds = {path: self._fd(path, keep=used_paths) for path in used_paths}
+        if native_io.lib() is not None:
+            try:
+                native_io.pread_batch([fds[path] for path in paths], pos, size, byte_buffer.ctypes.data, byte_off, threads=self.threads)
+            except OSError as e:
+                k = e.args[2] if len(e.args) > 2 else 0
+                raise kaldi_io.BadInputFormat("scp entry %r: %s" % (self.entries[int(indices[k])][1], e.args[1]))
+        else:
+            raw = memoryview(byte_buffer)
+            for k, path in enumerate(paths):
+                a, want, got = int(byte_off[k]), int(size[k]), 0
+                while got < want:
+                    r = os.preadv(fds[path], [raw[a + got:a + want]], int(pos[k]) + got)
+                    if r <= 0:
+                        raise kaldi_io.BadInputFormat("scp entry %r: the archive ends inside the matrix" % (self.entries[int(indices[k])][1],))
+                    got += r
+        if n:
+            counts = byte_buffer[(byte_off[:, None] + np.arange(8, 16, dtype=np.int64)[None]).ravel()].reshape(n, 8).view("<i4")
+            bad = np.flatnonzero((counts[:, 0] != rows) | (counts[:, 1] != cols))
+            if len(bad):
+                k = int(bad[0])
+                raise kaldi_io.BadInputFormat("scp entry %r: its header now says %d x %d, the header table %d x %d (the archive changed under the run?)" % (
+                    self.entries[int(indices[k])][1], int(counts[k, 0]), int(counts[k, 1]), int(rows[k]), int(cols[k])))
+        return byte_off, frame_off, formats, used
 
     def load_batch(self, indices):
         slow = {}
@@ -828,6 +996,14 @@ class ScpBatchLoader(object):
             raise kaldi_io.BadInputFormat("scp entry %r: %s" % (self.entries[int(idx[k])][1], e.args[1]))
 
 
+class CompressedGroup(object):
+    """What ScpGroupReader.read_group returns in the place of the row count for a group of compressed direct entries: the bodies lie
+    in the caller's byte buffer (ScpBatchLoader.load_compressed), the rows are still to be decoded (DeviceSets.submit_compressed)."""
+
+    def __init__(self, frames, byte_off, frame_off, formats, used_bytes):
+        self.frames, self.byte_off, self.frame_off, self.formats, self.used_bytes = frames, byte_off, frame_off, formats, used_bytes
+
+
 class ScpGroupReader(object):
     """kaldi_io.PackedArkReader's interface (peek_dim / read_group) over scp entries IN SCP ORDER: what extract_stream reads `scp:`
     input through when the run is not sharded - batches are written as they finish, memory is one batch, the keys print as they go
@@ -849,12 +1025,36 @@ class ScpGroupReader(object):
             return None
         return int(self.loader.shape(self._at, self._slow)[1])
 
-    def read_group(self, feats, max_utts=1024):
+    def has_compressed(self):
+        return self.loader.has_compressed()
+
+    def _compressed_bytes(self, i, cap, byte_cap):
+        """Bytes entry i takes in a byte buffer (its body, rounded up to 16) if it goes the compressed route: a compressed direct entry
+        whose rows fit a batch buffer and whose body fits the byte buffer; else 0 (host decode, as every other kind of entry)."""
+        h = self.loader._direct_compressed(i)
+        if h is None or h[2] > cap:
+            return 0
+        _, _, rows, cols, fmt = h                           # (libs.amd.frontend.compressed_body_bytes, on plain integers: once per entry)
+        size = (16 + (8 * cols + rows * cols if fmt == 1 else 2 * rows * cols if fmt == 2 else rows * cols) + 15) // 16 * 16
+        return size if size <= byte_cap else 0
+
+    def read_group(self, feats, max_utts=1024, byte_buffer=None):
+        """`byte_buffer` (uint8, e.g. DeviceSets.byte_buffer(k)): compressed direct entries are NOT decoded here - a group is cut where
+        the kind changes between them and everything else, and a group of them comes back as (keys, offsets, CompressedGroup) with the
+        bodies in byte_buffer; it is cut by rows exactly as any other group, and by the bytes the buffer holds."""
         cap, dim = feats.shape
         idx, offs, used = [], [0], 0
+        byte_cap = byte_buffer.shape[0] if byte_buffer is not None else 0
+        kind, used_bytes = None, 0
         while len(idx) < max_utts and self._at < len(self.entries):
             i = self._at
             rows, cols = self.loader.shape(i, self._slow)
+            if byte_buffer is not None:
+                size = self._compressed_bytes(i, cap, byte_cap)
+                if kind is None:
+                    kind = size > 0
+                if kind != (size > 0) or used_bytes + size > byte_cap:
+                    break
             if cols != dim:
                 raise kaldi_io.BadInputFormat("scp entry '%s' has %d columns, the table started with %d" % (self.entries[i][0], cols, dim))
             if rows > cap:
@@ -871,7 +1071,12 @@ class ScpGroupReader(object):
             used += rows
             offs.append(used)
             self._at += 1
+            if kind:
+                used_bytes += size
         offs = np.asarray(offs, dtype=np.int32)
+        if idx and kind:
+            byte_off, frame_off, formats, used_bytes = self.loader.load_compressed(idx, byte_buffer)
+            return [self.entries[i][0] for i in idx], offs, CompressedGroup(used, byte_off, frame_off, formats, used_bytes)
         if idx:
             self.loader.fill(idx, feats[:used], offs, self._slow)
             for i in idx:

@@ -563,6 +563,21 @@ int asv_select_frames(const float *feats, const unsigned char *voiced, const lon
 int asv_ingest_frames(const float *feats, const unsigned char *voiced, const long long *frame_offsets,
                       const long long *out_offsets, int n_utts, int dim, int cmn_window, int min_window, int center,
                       int norm_vars, float *out, void *stream);
+/* Kaldi compressed matrices ('CM ', 'CM2', 'CM3': what make_fbank.sh / make_mfcc.sh write with compress=true) -> packed
+ * float32 rows, on the stream in front of asv_ingest_frames / asv_net_extract.  bytes: device, the entries' BODIES as they
+ * lie on disk behind their token, each from its 16-byte global header {float min, float range, int32 rows, int32 cols}:
+ * 'CM ' = cols x 4 uint16 percentiles + cols x rows bytes column-major, 'CM2' = rows x cols uint16, 'CM3' = rows x cols
+ * uint8, both row-major.  byte_offsets: host int64 [n_utts], start of each body in `bytes`, a multiple of 16, increasing,
+ * bodies not overlapping; frame_offsets: host int64 [n_utts+1] from 0, rows of `out`; formats: host bytes [n_utts], 1 =
+ * 'CM ', 2 = 'CM2', 3 = 'CM3'; out: device [frame_offsets[n_utts]][dim] row-major.  The kernel reads min and range from
+ * the body; rows and cols come from frame_offsets and dim alone (the caller compares them with the header's counts - a
+ * body shorter than they say would be read past its end).  The result equals the host reader's
+ * (libs/support/kaldi_io.py) bit for bit: sequential float32 arithmetic, no FMA, correctly rounded divisions.
+ * Negative return: a null pointer, n_utts < 1, dim < 1, decreasing or overlapping offsets, a byte offset that is no
+ * multiple of 16, an unknown format.  The offsets are staged by the library as asv_ingest_frames stages its own: no
+ * stream synchronisation, the caller's arrays may be reused on return. */
+int asv_decode_compressed(const unsigned char *bytes, const long long *byte_offsets, const long long *frame_offsets,
+                          const unsigned char *formats, int n_utts, int dim, float *out, void *stream);
 /* Per-utterance mean / variance normalisation of every column, in place (kaldi_features.py:11-66
  * InputSequenceNormalization: mean over the frames, unbiased std floored at eps).  frame_offsets: host int64 [n_utts+1]. */
 int asv_cmvn(float *feats, const long long *frame_offsets, int n_utts, int dim, int mean_norm, int std_norm, float eps,

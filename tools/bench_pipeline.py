@@ -15,6 +15,11 @@ Two rates per run: `loop_utts_per_s` - the script's own clock around its read ->
 load, engine compilation and process start excluded) - and `end_to_end_utts_per_s` including all of that.
 
     python tools/bench_pipeline.py [--utts 50000] [--precisions f32x,bf16] [--paths stream,sharded] [--dir /tmp/asv_pipe]
+
+--compress writes the table as Kaldi 'CM ' compressed matrices (what make_fbank.sh / make_mfcc.sh write by default: a quarter of the
+bytes); the `scp` path then reads the bodies as they are and decodes them on the device, --device-decode 0 keeps the host decode
+(ASV_AMD_DEVICE_DECODE), and --script runs ANOTHER checkout's extract_embeddings.py on the same table (A/B between commits;
+profiles/decode_ab.txt).
 """
 import argparse
 import json
@@ -29,9 +34,35 @@ sys.path.insert(0, os.path.join(REPO, "asv-subtools_amd", "pytorch"))
 SCRIPT = os.path.join(REPO, "asv-subtools_amd", "pytorch", "pipeline", "onestep", "extract_embeddings.py")
 
 
-def prepare(directory, utts, frames=200, dim=80, lengths=None):
+def compress_cm(mat):
+    """The 'CM ' entry (from `\\0B` on) of a float32 matrix, after Kaldi's compressed-matrix.cc: global min / range, per column the 0 / 25 /
+    75 / 100 % order statistics as uint16 (kept strictly increasing), every value as a byte on the three linear pieces between them."""
+    import numpy as np
+    mat = np.asarray(mat, dtype=np.float32)
+    rows, cols = mat.shape
+    gmin, gmax = float(mat.min()), float(mat.max())
+    grange = max(gmax - gmin, 1e-10 * max(1.0, abs(gmin)))
+    srt = np.sort(mat, axis=0)
+    q = np.stack([srt[0], srt[rows // 4], srt[3 * rows // 4], srt[rows - 1]], axis=1).astype(np.float64)           # [cols, 4]
+    u = np.floor((q - gmin) / grange * 65535.0 + 0.499).astype(np.int64)
+    u[:, 0] = np.minimum(u[:, 0], 65532)
+    u[:, 1] = np.minimum(np.maximum(u[:, 1], u[:, 0] + 1), 65533)
+    u[:, 2] = np.minimum(np.maximum(u[:, 2], u[:, 1] + 1), 65534)
+    u[:, 3] = np.minimum(np.maximum(u[:, 3], u[:, 2] + 1), 65535)
+    p = gmin + grange * u / 65535.0                                                                                # the percentiles as the reader sees them
+    v = mat.T.astype(np.float64)                                                                                   # [cols, rows]: the stored order
+    p0, p25, p75, p100 = (p[:, i:i + 1] for i in range(4))
+    lo = np.clip(np.floor((v - p0) / (p25 - p0) * 64.0 + 0.5), 0, 64)
+    mid = np.clip(64 + np.floor((v - p25) / (p75 - p25) * 128.0 + 0.5), 64, 192)
+    hi = np.clip(192 + np.floor((v - p75) / (p100 - p75) * 63.0 + 0.5), 192, 255)
+    data = np.where(v < p25, lo, np.where(v < p75, mid, hi)).astype(np.uint8)
+    return b"\0BCM " + np.array([gmin, grange], dtype="<f4").tobytes() + np.array([rows, cols], dtype="<i4").tobytes() + u.astype("<u2").tobytes() + data.tobytes()
+
+
+def prepare(directory, utts, frames=200, dim=80, lengths=None, compress=False):
     """feats.ark + feats.scp + final.params + nnet.config in `directory`; returns their paths and the seconds spent writing.
-    lengths = (lo, hi): utterance i has one of 64 lengths drawn from U[lo, hi] (a ragged table) instead of `frames` everywhere."""
+    lengths = (lo, hi): utterance i has one of 64 lengths drawn from U[lo, hi] (a ragged table) instead of `frames` everywhere.
+    compress: the matrices are written as 'CM ' compressed entries instead of float32."""
     import numpy as np
     import torch
     from libs.support import kaldi_io
@@ -49,7 +80,10 @@ def prepare(directory, utts, frames=200, dim=80, lengths=None):
     feats, scp = os.path.join(directory, "feats.ark"), os.path.join(directory, "feats.scp")
     lens = [frames] * 64 if lengths is None else [int(v) for v in np.random.RandomState(7).randint(lengths[0], lengths[1] + 1, size=64)]
     base = [synth.synth_feats(lens[i], dim, 50_000 + i) for i in range(64)]
-    payload = [b"\0BFM \4" + np.int32(m.shape[0]).tobytes() + b"\4" + np.int32(dim).tobytes() + m.tobytes() for m in base]
+    if compress:
+        payload = [compress_cm(m) for m in base]
+    else:
+        payload = [b"\0BFM \4" + np.int32(m.shape[0]).tobytes() + b"\4" + np.int32(dim).tobytes() + m.tobytes() for m in base]
     t0 = time.perf_counter()
     with open(feats, "wb") as f, open(scp, "w") as s:
         pos = 0
@@ -65,14 +99,16 @@ def prepare(directory, utts, frames=200, dim=80, lengths=None):
             "mean_frames": float(np.mean([lens[(i * 37) % 64 if lengths is not None else i % 64] for i in range(min(utts, 6400))]))}
 
 
-def run_once(files, path, precision, utts, out_dir, timeout=900):
+def run_once(files, path, precision, utts, out_dir, timeout=900, script=None, device_decode=None):
     from libs.support import kaldi_io
     out = os.path.join(out_dir, "xvector_%s_%s.ark" % (path, precision))
     rspec = "ark:" + files["ark"] if path == "stream" else "scp:" + files["scp"]
     extra = ["--sharded", "true"] if path == "sharded" else []
     env = dict(os.environ, ASV_AMD_PRECISION=precision, ASV_AMD_REPORT_TIMING="1")
+    if device_decode is not None:
+        env["ASV_AMD_DEVICE_DECODE"] = "1" if device_decode else "0"
     t0 = time.perf_counter()
-    res = subprocess.run([sys.executable, SCRIPT, "--nnet-config", files["cfg"], "--use-gpu", "true", "--gpu-id", "0"] + extra + [files["params"], rspec, "ark:" + out],
+    res = subprocess.run([sys.executable, script or SCRIPT, "--nnet-config", files["cfg"], "--use-gpu", "true", "--gpu-id", "0"] + extra + [files["params"], rspec, "ark:" + out],
                          capture_output=True, text=True, env=env, timeout=timeout)
     dt = time.perf_counter() - t0
     if res.returncode != 0:
@@ -87,14 +123,17 @@ def run_once(files, path, precision, utts, out_dir, timeout=900):
     m = re.search(r"consumer thread: (.*)", res.stdout)
     if m:
         rec["consumer_thread_seconds"] = {k: float(v) for k, v in re.findall(r"(\w+) ([0-9.]+) s", m.group(1))}
+    m = re.search(r"submit pieces: (.*)", res.stdout)
+    if m:
+        rec["submit_seconds"] = {k: float(v) for k, v in re.findall(r"(\w+) ([0-9.]+) s", m.group(1))}
     return rec
 
 
 def measure(utts=50000, frames=200, precisions=("f32x", "bf16"), paths=("stream", "scp", "sharded"), directory="/tmp/asv_pipe", keep=False,
-            repeats_in_both_orders=True, lengths=None):
-    files = prepare(directory, utts, frames, lengths=lengths)
+            repeats_in_both_orders=True, lengths=None, compress=False, script=None, device_decode=None):
+    files = prepare(directory, utts, frames, lengths=lengths, compress=compress)
     try:
-        return _measure(files, utts, frames, precisions, paths, directory, repeats_in_both_orders, lengths)
+        return _measure(files, utts, frames, precisions, paths, directory, repeats_in_both_orders, lengths, compress, script, device_decode)
     finally:
         # a failing or timed-out run must not leave gigabytes in /tmp
         if not keep:
@@ -112,10 +151,10 @@ def measure(utts=50000, frames=200, precisions=("f32x", "bf16"), paths=("stream"
                 pass
 
 
-def _measure(files, utts, frames, precisions, paths, directory, repeats_in_both_orders, lengths):
+def _measure(files, utts, frames, precisions, paths, directory, repeats_in_both_orders, lengths, compress=False, script=None, device_decode=None):
     shape = "%d" % frames if lengths is None else "U[%d, %d] (mean %.0f)" % (lengths[0], lengths[1], files["mean_frames"])
-    out = {"workload": "%d utterances x %s x 80 f32 Kaldi ark (%.2f GB, page cache) -> x-vector ark through pipeline/onestep/extract_embeddings.py, one GPU" % (
-               utts, shape, files["bytes"] / 1e9),
+    out = {"workload": "%d utterances x %s x 80 %s Kaldi ark (%.2f GB, page cache) -> x-vector ark through pipeline/onestep/extract_embeddings.py, one GPU" % (
+               utts, shape, "'CM ' compressed" if compress else "f32", files["bytes"] / 1e9),
            "ark_write_seconds_synthetic": round(files["write_seconds"], 2), "host_cores": os.cpu_count(), "runs": {}}
     # One short untimed run per path first: a fresh box reads the code it has never run - RCCL's collective kernels, torch's cat / index
     # kernels of the gather, the script's own modules - from a cold file cache (the first --sharded run of a container measured 0.1 s
@@ -135,7 +174,7 @@ def _measure(files, utts, frames, precisions, paths, directory, repeats_in_both_
     with open(files["ark"], "rb") as f, open(warm["ark"], "wb") as g:
         g.write(f.read(warm_bytes))
     for path in paths:
-        run_once(warm, path, precisions[0], n_warm, directory)
+        run_once(warm, path, precisions[0], n_warm, directory, script=script, device_decode=device_decode)
     for k in ("ark", "scp"):
         os.remove(warm[k])
     out["warm_up"] = "one untimed run of %d utterances per path (cold code pages of a fresh box)" % n_warm
@@ -147,7 +186,7 @@ def _measure(files, utts, frames, precisions, paths, directory, repeats_in_both_
     for prec in precisions:
         order = list(paths) + (list(reversed(paths)) if repeats_in_both_orders and len(paths) > 1 else [])
         for path in order:
-            rec = run_once(files, path, prec, utts, directory)
+            rec = run_once(files, path, prec, utts, directory, script=script, device_decode=device_decode)
             name = "%s_%s" % (path, prec)
             out["all_runs"].append(dict(rec, run=name))
             best = out["runs"].get(name)
@@ -165,10 +204,14 @@ def main():
     ap.add_argument("--dir", default="/tmp/asv_pipe")
     ap.add_argument("--lengths", default="", help="lo,hi: a ragged table (64 lengths drawn from U[lo, hi]) instead of --frames everywhere")
     ap.add_argument("--once", action="store_true", help="one run per (path, precision) instead of both positions of the sequence")
+    ap.add_argument("--compress", action="store_true", help="write the table as 'CM ' compressed matrices (Kaldi's default) instead of float32")
+    ap.add_argument("--script", default="", help="another checkout's extract_embeddings.py to run on the table (A/B between commits)")
+    ap.add_argument("--device-decode", default="", choices=["", "0", "1"], help="ASV_AMD_DEVICE_DECODE of the runs (default: the script's own default)")
     args = ap.parse_args()
     lengths = tuple(int(v) for v in args.lengths.split(",")) if args.lengths else None
     print(json.dumps(measure(args.utts, args.frames, tuple(args.precisions.split(",")), tuple(args.paths.split(",")), args.dir, repeats_in_both_orders=not args.once,
-                             lengths=lengths)))
+                             lengths=lengths, compress=args.compress, script=args.script or None,
+                             device_decode=None if args.device_decode == "" else args.device_decode == "1")))
 
 
 if __name__ == "__main__":
