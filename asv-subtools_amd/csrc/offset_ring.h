@@ -1,5 +1,5 @@
 // Host offset arrays of a C-ABI call, staged to the device without a host wait: shared by the entry points that take per-utterance
-// host offsets and launch on the caller's stream (asv_ingest_frames, asv_decode_compressed).  Each of them keeps its OWN thread_local
+// host offsets and launch on the caller's stream (asv_ingest_frames, asv_ingest_windows, asv_decode_compressed).  Each of them keeps its OWN thread_local
 // ring, so the offsets of one do not evict the other's.
 #pragma once
 
@@ -12,7 +12,7 @@
 
 namespace asv {
 
-// The two host offset arrays of a call, on the device.  Per calling thread: a ring of page-locked staging slots, each with its device
+// The two (or three: `c`) host offset arrays of a call, one behind the other on the device.  Per calling thread: a ring of page-locked staging slots, each with its device
 // twin.  Unchanged contents (fixed batch shapes) reuse the last upload, changed ones take the next slot and copy asynchronously - the
 // host never waits for the stream either way (the extraction loops submit new offsets per batch, alternating between two streams).
 // Ordering is by events, whichever streams the calls of a thread use:
@@ -40,7 +40,7 @@ struct OffsetRing {
     k.n_readers = 0;
     return ASV_OK;
   }
-  int get(const long long *a, const long long *b, size_t each, hipStream_t s, const long long **out) {
+  int get(const long long *a, const long long *b, size_t each, hipStream_t s, const long long **out, const long long *c = nullptr) {
     int cur = 0;
     ASV_HIP_CHECK(hipGetDevice(&cur));
     if (device != cur) {                                                      // (another device: start over there)
@@ -54,9 +54,10 @@ struct OffsetRing {
       }
       device = cur;
     }
-    const size_t count = 2 * each;
+    const size_t count = (c ? 3 : 2) * each;
     Slot &l = slot[at];
-    if (l.dev && l.count == count && memcmp(l.host, a, each * 8) == 0 && memcmp(l.host + each, b, each * 8) == 0) {
+    if (l.dev && l.count == count && memcmp(l.host, a, each * 8) == 0 && memcmp(l.host + each, b, each * 8) == 0 &&
+        (!c || memcmp(l.host + 2 * each, c, each * 8) == 0)) {
       if (s != l.stream) ASV_HIP_CHECK(hipStreamWaitEvent(s, l.uploaded, 0));   // the copy was queued on another stream: this one waits for it
       *out = l.dev;
       return ASV_OK;
@@ -75,6 +76,7 @@ struct OffsetRing {
     }
     memcpy(k.host, a, each * 8);
     memcpy(k.host + each, b, each * 8);
+    if (c) memcpy(k.host + 2 * each, c, each * 8);
     k.count = 0;                                                              // (not reusable until the copy is queued and marked)
     ASV_HIP_CHECK(hipMemcpyAsync(k.dev, k.host, count * 8, hipMemcpyHostToDevice, s));
     ASV_HIP_CHECK(hipEventRecord(k.uploaded, s));

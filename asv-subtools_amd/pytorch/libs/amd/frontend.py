@@ -270,6 +270,38 @@ def ingest(feats, frame_off, voiced=None, cmn_window=0, min_window=100, center=T
     return out[:rows], kept_off
 
 
+def ingest_windows(feats, win_start, win_len, cmn_window=0, min_window=100, center=True, norm_vars=False, out=None):
+    """Windows of rows that lie on the device -> the rows the extractor reads, in one launch (asv_ingest_windows): window w is rows
+    [win_start[w], win_start[w] + win_len[w]) of `feats` ([rows, dim] f32 CUDA tensor: one parent matrix or several, packed) and an
+    utterance of its own for Kaldi's apply-cmvn-sliding - what the reference's sliding (diarisation) mode computes through range-specified
+    scp entries.  Windows may overlap, repeat and come in any order; an empty one writes nothing.  cmn_window=0: the rows are copied as
+    they are.  Returns (rows [sum win_len, dim] f32 CUDA tensor - `out[:sum win_len]` when `out` is given -, offsets int64 numpy [n + 1] of
+    the windows in it); bit for bit what ingest() gives for a packed copy of the windows."""
+    import torch
+    win_start, win_len = _off(win_start), _off(win_len)
+    n = len(win_start)
+    if feats.dim() != 2 or feats.dtype != torch.float32 or not feats.is_cuda or not feats.is_contiguous():
+        raise ValueError("ingest_windows: feats must be a contiguous [rows, dim] f32 CUDA tensor")
+    if n < 1 or win_start.ndim != 1 or win_len.shape != win_start.shape:
+        raise ValueError("ingest_windows: one start and one length per window, at least one window")
+    if (win_start < 0).any() or (win_len < 0).any() or (win_start + win_len > feats.shape[0]).any():
+        raise ValueError("ingest_windows: a window lies outside the %d rows of feats" % feats.shape[0])
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(win_len, out=offsets[1:])
+    rows = int(offsets[-1])
+    if out is None:
+        out = torch.empty((rows, feats.shape[1]), dtype=torch.float32, device=feats.device)
+    elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != feats.shape[1] or out.shape[0] < rows:
+        raise ValueError("ingest_windows: out must be a contiguous f32 CUDA tensor of at least [%d, %d]" % (rows, feats.shape[1]))
+    if rows == 0:
+        return out[:0], offsets                            # nothing but empty windows: no launch (an empty tensor has no address to hand over)
+    with torch.cuda.device(feats.device):
+        capi.check(capi.lib().asv_ingest_windows(C.c_void_p(feats.data_ptr()), feats.shape[0], _i64p(win_start), _i64p(win_len), n, feats.shape[1],
+                                                 int(cmn_window), int(min_window), int(bool(center)), int(bool(norm_vars)), C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(torch.cuda.current_stream(feats.device).cuda_stream)), "asv_ingest_windows")
+    return out[:rows], offsets
+
+
 COMPRESSED_FORMATS = {"CM ": 1, "CM2": 2, "CM3": 3}          # Kaldi's token -> the format byte of asv_decode_compressed
 
 

@@ -47,10 +47,13 @@ class DeviceSets(object):
     staging buffer (byte_buffer(k), filled by ScpBatchLoader.load_compressed) with its device twin, and submit_compressed() copies the
     bytes used and decodes them on the engine's stream (asv_decode_compressed) into the rows submit() would have copied, then goes on as
     submit() does.  A quarter of the H2D bytes, and no decode on the host.
+    windows=True (with ingest=, without flags): submit_windows() takes the rows of a set as PARENT matrices and a list of windows of them
+    (the reference's sliding / diarisation mode) - one launch (asv_ingest_windows) gathers and normalises every window as an utterance of
+    its own into the rows the engine reads; overlapping windows are uploaded once.
     ASV_AMD_PIPELINE_ENGINES=1 keeps one engine on one stream (device-resident rate of two: +5 % x-vector, +9 % ECAPA, +19 %
     ResNet34-SE, profiles/r3h_streams.txt)."""
 
-    def __init__(self, model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", n_engines=2, warm=True, ingest=None, compressed=False):
+    def __init__(self, model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", n_engines=2, warm=True, ingest=None, compressed=False, windows=False):
         import torch
         assert results in ("host", "device")
         self.torch = torch
@@ -90,6 +93,11 @@ class DeviceSets(object):
                 self.host_flags = [torch.zeros(batch_frames, dtype=torch.uint8).pin_memory() for _ in range(n_sets)]
                 self.flags_np = [t.numpy() for t in self.host_flags]
                 self.dev_flags = [torch.empty(batch_frames, dtype=torch.uint8, device=dev) for _ in range(n_sets)]
+        if windows and (ingest is None or ingest.flags):
+            raise ValueError("windows=True needs ingest=IngestOptions(...) without flags: the raw rows need a device buffer of their own, "
+                             "and the reference's sliding mode has no VAD")
+        self.windows = bool(windows)
+        self.batch_utts = int(batch_utts)
         self.host_bytes = self.bytes_np = self.dev_bytes = None                          # compressed=False: nothing is allocated, nothing is launched
         if compressed:
             # the worst case of a full batch: 'CM2' takes 2 bytes per value, every body its global header, 'CM ' its column headers, and
@@ -117,6 +125,8 @@ class DeviceSets(object):
                         eng.extract_device(self.dev_in[0][:int(offs[-1])], offs, max_chunk=self.max_chunk)
                         if ingest is not None:         # (the ingest kernel's code object, and this thread's offset staging in the library)
                             self._ingest(self.dev_in[0][:int(offs[-1])], offs.astype(np.int64), None, None, self.dev_raw[0])
+                        if self.windows:               # (the windows kernel's code object and its staging: asked for by the caller alone)
+                            self._ingest_windows(self.dev_in[0][:int(offs[-1])], (offs[:-1].astype(np.int64), np.diff(offs).astype(np.int64)), self.dev_raw[0])
                         if compressed:                 # (the decode kernel's code object and its offset staging; a one-row 'CM3' body of zeros)
                             self._decode(self.dev_bytes[0], np.zeros(1, dtype=np.int64), np.array([0, 1], dtype=np.int64), np.full(1, 3, dtype=np.uint8),
                                          (self.dev_in if ingest is None else self.dev_raw)[0])
@@ -149,6 +159,53 @@ class DeviceSets(object):
         return frontend.ingest(raw, raw_off, voiced=dev_flags, cmn_window=o.cmn_window, min_window=o.min_window, center=o.center,
                                norm_vars=o.norm_vars, out=out, kept_off=kept_off)[0]
 
+    def _ingest_windows(self, raw, windows, out):
+        from . import frontend
+        o = self.ingest
+        return frontend.ingest_windows(raw, windows[0], windows[1], cmn_window=o.cmn_window, min_window=o.min_window, center=o.center,
+                                       norm_vars=o.norm_vars, out=out)[0]
+
+    def submit_windows(self, k, frames, win_start, win_len, packed=None):
+        """The first `frames` rows of host_buffer(k) are RAW rows of parent matrices; window w is rows [win_start[w], win_start[w] +
+        win_len[w]) of them and becomes one utterance: copied once, then gathered and normalised per window (asv_ingest_windows, the
+        options of `ingest`) into the rows the engine reads - everything behind that is submit()'s.  `packed` = (byte_off, frame_off,
+        formats, used_bytes): the rows lie in byte_buffer(k) as compressed bodies instead and are decoded on the device first, as
+        submit_compressed() does.  `frames` may also be a [rows, dim] f32 CUDA tensor of the caller's (rows that are on the device
+        already, e.g. one long parent whose windows take several batches): nothing is copied; the caller has made sure that the tensor
+        is complete before the call and keeps it alive until finish(k)."""
+        torch = self.torch
+        if not self.windows:
+            raise ValueError("these buffer sets were made without windows=True")
+        start, rows = np.ascontiguousarray(win_start, dtype=np.int64), np.ascontiguousarray(win_len, dtype=np.int64)
+        if start.ndim != 1 or start.shape != rows.shape or not 1 <= len(start) <= self.batch_utts:
+            raise ValueError("submit_windows: between 1 and batch_utts windows, one start and one length each (got %d)" % len(start))
+        cap = self.dev_in[k].shape[0]
+        resident = isinstance(frames, torch.Tensor)
+        if resident:
+            if frames.dim() != 2 or frames.dtype != torch.float32 or frames.device != self.dev or not frames.is_contiguous() or frames.shape[1] != self.dev_in[k].shape[1]:
+                raise ValueError("submit_windows: resident rows must be a contiguous [rows, %d] f32 tensor on %s" % (self.dev_in[k].shape[1], self.dev))
+            have = frames.shape[0]
+        else:
+            have = frames = int(frames)
+            if not 0 < have <= cap:
+                raise ValueError("submit_windows: %d raw rows do not fit the buffer set (%d rows)" % (have, cap))
+        if (start < 0).any() or (rows < 1).any() or (start + rows > have).any():
+            raise ValueError("submit_windows: a window is empty or lies outside the %d raw rows" % have)
+        offsets = np.zeros(len(start) + 1, dtype=np.int64)
+        np.cumsum(rows, out=offsets[1:])
+        if int(offsets[-1]) > cap:
+            raise ValueError("submit_windows: the windows hold %d rows, the buffer set %d" % (int(offsets[-1]), cap))
+        if packed is not None:
+            if self.dev_bytes is None or resident:
+                raise ValueError("submit_windows: compressed bodies need buffer sets made with compressed=True (and rows of the set's own)")
+            byte_off, frame_off, formats, used_bytes = packed
+            frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+            if int(frame_off[-1]) != have or not 0 < int(used_bytes) <= self.dev_bytes[k].shape[0]:
+                raise ValueError("submit_windows: the compressed bodies hold %d rows in %d bytes, the call says %d rows (byte buffer: %d)" % (
+                    int(frame_off[-1]), int(used_bytes), have, self.dev_bytes[k].shape[0]))
+            packed = (np.ascontiguousarray(byte_off, dtype=np.int64), frame_off, formats, int(used_bytes))
+        return self._submit(k, offsets.astype(np.int32), frames, packed, None, None, windows=(start, rows))
+
     def submit(self, k, offsets, frames, voiced=None, kept_off=None):
         """`voiced` (ingest with flags): one uint8 flag per raw row - flag_buffer(k)[:frames] as the reader filled it, or an array of its
         own; `kept_off`: its per-utterance running sum where the caller has it already (frontend.kept_offsets)."""
@@ -166,10 +223,11 @@ class DeviceSets(object):
                 rows, used_bytes, self.dev_in[k].shape[0], self.dev_bytes[k].shape[0]))
         return self._submit(k, frame_off.astype(np.int32), rows, (np.ascontiguousarray(byte_off, dtype=np.int64), frame_off, formats, used_bytes), voiced, kept_off)
 
-    def _submit(self, k, offsets, frames, packed, voiced, kept_off):
+    def _submit(self, k, offsets, frames, packed, voiced, kept_off, windows=None):
         """submit() (`packed` None: `frames` rows of host_buffer(k), or an array of its own) and submit_compressed() (`packed` = (byte_off,
         frame_off, formats, used_bytes) of byte_buffer(k)): they differ in what is copied to the device and in the decode launch behind
-        the copy - the flags, the ingest, the extraction, the result copy and the status word are the same code."""
+        the copy - the flags, the ingest, the extraction, the result copy and the status word are the same code.  `windows` (submit_windows:
+        (start, rows) of every window of the raw rows; `offsets` are then the windows' own) swaps the ingest launch for the windows one."""
         torch = self.torch
         assert self.pending[k] is None, "set %d still holds a batch: finish() it first" % k
         n = len(offsets) - 1
@@ -210,7 +268,9 @@ class DeviceSets(object):
         t = [time.perf_counter()]
         with torch.cuda.device(self.dev), torch.cuda.stream(self.streams[e]):
             own = packed is None and isinstance(frames, np.ndarray)
-            if packed is not None:                       # compressed bodies: only the bytes used travel; the rows are decoded behind the copy
+            if isinstance(frames, torch.Tensor):         # (submit_windows: rows that are on the device already)
+                feats = frames
+            elif packed is not None:                     # compressed bodies: only the bytes used travel; the rows are decoded behind the copy
                 self.dev_bytes[k][:packed[3]].copy_(self.host_bytes[k][:packed[3]], non_blocking=True)
                 feats = (self.dev_in if self.ingest is None else self.dev_raw)[k][:frames]
             elif own:                                    # one utterance longer than a whole batch buffer: a pageable copy of its own
@@ -233,7 +293,10 @@ class DeviceSets(object):
             if packed is not None:
                 self._decode(self.dev_bytes[k], packed[0], packed[1], packed[2], feats)
                 t.append(time.perf_counter())
-            if self.ingest is not None:                  # raw rows -> normalised kept rows, compacted: what the engine (and a range re-run) reads
+            if windows is not None:                      # raw parent rows -> one normalised utterance per window: what the engine (and a range re-run) reads
+                feats = self._ingest_windows(feats, windows, self.dev_in[k])
+                t.append(time.perf_counter())
+            elif self.ingest is not None:                # raw rows -> normalised kept rows, compacted: what the engine (and a range re-run) reads
                 feats = self._ingest(feats, raw_off, flags, kept_off, None if own else self.dev_in[k])
                 t.append(time.perf_counter())
             if self.results == "host":

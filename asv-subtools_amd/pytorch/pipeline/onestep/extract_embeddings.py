@@ -27,6 +27,15 @@ input (not --sharded) the bodies of such 'file:offset' entries are read as they 
 (asv_decode_compressed) in front of the ingest / the extraction: the same float32 rows, bit for bit, as the host reader's.  Range-specified entries,
 pipes, text and float64 matrices go through the host reader as before; ASV_AMD_DEVICE_DECODE=0 sends everything there.
 
+Sliding (diarisation) mode: `--sliding true --segments data/segments [--window 1.5 --period 0.75 --min-segment 0.5 --hard-min false
+--frame-shift 0.01 --subsegments-out subsegments]` is the `sliding=true` branch of the reference's shell script
+(pipeline/extract_xvectors_for_pytorch.sh:57-84): every segment is cut into uniform overlapping sub-segments
+(libs.amd.subsegments, the rules of kaldi/utils/data/get_uniform_subsegments.py and subsegment_data_dir.sh) and one vector per
+sub-segment is written under the sub-segment's id.  The reference reads each sub-segment as a range 'file:offset[first:last]' of its
+parent - the whole parent per window; here a parent is read and uploaded once per batch and the windows are built on the device
+(asv_ingest_windows), --cmn-window applying per window as it does in the reference's pipe.  `scp:` input only, no --vad-scp (the
+reference replaces the VAD by all ones in this mode), not with --sharded.
+
 Multi-GPU (--sharded true, launched as `python -m torch.distributed.run --nproc-per-node N ... extract_embeddings.py ...`, one
 process per GPU): replaces the reference's `nj` jobs over a length-balanced split of feats.scp and the final
 `cat xvector.JOB.scp` (pipeline/extract_xvectors_for_pytorch.sh:90-100,125-151; splitDataByLength.sh:44-80).  Every rank reads
@@ -36,6 +45,7 @@ vectors in scp order.
 """
 
 import argparse
+import collections
 import os
 import re
 import sys
@@ -71,6 +81,15 @@ def get_args(argv=None):
     parser.add_argument("--cmn-norm-vars", type=str, default="false", choices=["true", "false"], help="apply-cmvn-sliding --norm-vars.")
     parser.add_argument("--cmn-min-window", type=int, default=100, help="apply-cmvn-sliding --min-cmn-window; only read when not centred.")
     parser.add_argument("--vad-scp", type=str, default="", help="Kaldi scp of per-frame VAD vectors: select-voiced-frames on the device.")
+    parser.add_argument("--sliding", type=str, default="false", choices=["true", "false"],
+                        help="Diarisation mode of the reference's extract_xvectors_for_pytorch.sh: one vector per uniform sub-segment of every segment.")
+    parser.add_argument("--segments", type=str, default="", help="Kaldi segments file of the data directory (sliding mode); its first field is a key of the scp.")
+    parser.add_argument("--window", type=float, default=1.5, help="Sub-segment length in seconds (sliding mode).")
+    parser.add_argument("--period", type=float, default=0.75, help="Sub-segment shift in seconds (sliding mode).")
+    parser.add_argument("--min-segment", type=float, default=0.5, help="Shortest remainder that becomes a sub-segment of its own (sliding mode).")
+    parser.add_argument("--hard-min", type=str, default="false", choices=["true", "false"], help="Drop segments shorter than --min-segment first (sliding mode).")
+    parser.add_argument("--frame-shift", type=float, default=0.01, help="Seconds per feature row (sliding mode).")
+    parser.add_argument("--subsegments-out", type=str, default="", help="Write the sub-segments here: '<new-utt> <utt> <start> <end>' (sliding mode).")
     parser.add_argument("model_path", metavar="model-path", type=str, help="The model used to extract embeddings.")
     parser.add_argument("feats_rspecifier", metavar="feats-rspecifier", type=str, help="")
     parser.add_argument("vectors_wspecifier", metavar="vectors-wspecifier", type=str, help="")
@@ -91,6 +110,35 @@ def ingest_options(args):
     if args.cmn_window == 0 and not args.vad_scp:
         return None
     return IngestOptions(args.cmn_window, args.cmn_min_window, center, utils.to_bool(args.cmn_norm_vars), bool(args.vad_scp))
+
+
+SlidingOptions = collections.namedtuple("SlidingOptions", "segments window period min_segment hard_min frame_shift subsegments_out")
+
+
+def sliding_options(args):
+    """The sliding (diarisation) mode of the command line, or None.  What the mode does not take is refused here, before anything is
+    set up: each would be a change of its own."""
+    if not utils.to_bool(args.sliding):
+        return None
+    if utils.to_bool(args.sharded):
+        raise ValueError("--sliding true does not take --sharded true: sharding the windows of a parent over ranks (and uploading it on each) is not built")
+    if args.vad_scp:
+        raise ValueError("--sliding true does not take --vad-scp: the reference replaces the VAD by all ones in this mode (createVisualVad.sh)")
+    if not _SCP_PREFIX.match(args.feats_rspecifier):
+        raise ValueError("--sliding true needs random access to the parents' rows: pass 'scp:feats.scp', not %r" % args.feats_rspecifier)
+    if not args.segments:
+        raise ValueError("--sliding true needs --segments: the Kaldi segments file whose segments are cut into windows")
+    if not (args.window > 0 and 0 < args.period and args.min_segment >= 0 and args.frame_shift > 0):
+        raise ValueError("--sliding true needs positive --window, --period and --frame-shift (got %r, %r, %r)" % (args.window, args.period, args.frame_shift))
+    return SlidingOptions(args.segments, args.window, args.period, args.min_segment, utils.to_bool(args.hard_min), args.frame_shift, args.subsegments_out)
+
+
+def refuse_ranged_entries(entries):
+    """Sliding mode addresses the rows of a parent by the windows' own ranges: a source entry that carries one already is refused
+    (the reference would go through normalize_data_range.pl)."""
+    for key, rxfile in entries:
+        if _RANGE.search(rxfile):
+            raise ValueError("--sliding true: scp entry %r carries a range specifier (%s): windows of ranges are not built" % (key, rxfile))
 
 
 class VadTable(object):
@@ -872,6 +920,46 @@ class ScpBatchLoader(object):
                     raise kaldi_io.BadInputFormat("scp entry %r: the archive ends inside the matrix" % (self.entries[indices[k]][1],))
                 got += r
 
+    def fill_rows(self, spans, packed):
+        """Rows of parents into a packed buffer (the sliding mode): `spans` = [(entry, row0, row1, at)] - rows [row0, row1) of entry's
+        matrix go to packed[at:at + row1 - row0].  A plain float32 direct entry costs one positioned read of exactly those rows (all of
+        a call's in one native call); every other kind is decoded on the host - ONCE per parent: the last decoded matrix is kept, the
+        spans of a long parent follow one another."""
+        from libs.support import native_io
+        dim = packed.shape[1]
+        fds, pos, size, at_byte, who = [], [], [], [], []
+        for i, row0, row1, at in spans:
+            h = self._direct(i)
+            if h is not None and h[3] == dim and 0 <= row0 <= row1 <= h[2]:
+                fds.append(h[0]); pos.append(h[1] + row0 * dim * 4); size.append((row1 - row0) * dim * 4); at_byte.append(at * dim * 4); who.append(i)
+                continue
+            if getattr(self, "_last_parent", (None, None))[0] != i:
+                self._last_parent = (i, self(i))
+            m = self._last_parent[1]
+            if m.shape[1] != dim or row1 > m.shape[0]:
+                raise kaldi_io.BadInputFormat("scp entry %r is %d x %d: rows %d:%d of %d columns were asked for" % (
+                    self.entries[i][1], m.shape[0], m.shape[1], row0, row1, dim))
+            packed[at:at + row1 - row0] = m[row0:row1]
+        if not who:
+            return
+        paths = set(fds)
+        fds = [self._fd(path, keep=paths) for path in fds]
+        if native_io.lib() is not None:
+            try:
+                native_io.pread_batch(fds, pos, size, packed.ctypes.data, at_byte, threads=self.threads)
+            except OSError as e:
+                k = e.args[2] if len(e.args) > 2 else 0
+                raise kaldi_io.BadInputFormat("scp entry %r: %s" % (self.entries[who[k]][1], e.args[1]))
+            return
+        raw = memoryview(packed.reshape(-1).view(np.uint8))
+        for k in range(len(who)):
+            got = 0
+            while got < size[k]:
+                r = os.preadv(fds[k], [raw[at_byte[k] + got:at_byte[k] + size[k]]], pos[k] + got)
+                if r <= 0:
+                    raise kaldi_io.BadInputFormat("scp entry %r: the archive ends inside the matrix" % (self.entries[who[k]][1],))
+                got += r
+
     def load_compressed(self, indices, byte_buffer):
         """The BODIES of the compressed direct entries `indices` (each from its 16-byte global header, as it lies in the file), read in one
         native call into the caller's uint8 `byte_buffer` (e.g. the page-locked staging buffer of libs.amd.pipeline.DeviceSets), every
@@ -1084,6 +1172,152 @@ class ScpGroupReader(object):
         return [self.entries[i][0] for i in idx], offs, used
 
 
+def sliding_windows(entries, lengths, opts, warn=None):
+    """The windows of a sliding run: (ids, windows, subsegments) - `windows` = [(entry index, first row, rows)] in processing order
+    (the parents in scp order, each one's windows in start order), `ids` the sub-segment ids the vectors are written under,
+    `subsegments` everything libs.amd.subsegments.uniform_subsegments made of the segments file (what --subsegments-out holds)."""
+    from libs.amd import subsegments
+    keys = entries.keys() if hasattr(entries, "plain_index") else [k for k, _ in entries]
+    index = {}
+    for i, key in enumerate(keys):
+        index.setdefault(key, i)
+    with kaldi_io.open_or_fd(opts.segments, "rb") as f:
+        lines = [line for line in f.read().decode("latin1").splitlines() if line.strip()]
+    for line in lines:
+        if len(line.split()) < 4:
+            raise ValueError("--segments %s: a line needs '<utt> <rec> <start> <end>', got %r" % (opts.segments, line))
+        if line.split()[0] not in index:
+            raise ValueError("--segments %s: %r is not a key of the features' scp" % (opts.segments, line.split()[0]))
+    subs = subsegments.uniform_subsegments(lines, opts.window, opts.period, opts.min_segment, True, opts.hard_min)
+    num_frames = {utt: int(lengths[index[utt]]) for utt in {s[1] for s in subs}}
+    kept, first, last = subsegments.frame_ranges(subs, num_frames, opts.frame_shift,
+                                                 warn=warn if warn is not None else (lambda line: print("WARNING: " + line, file=sys.stderr)))
+    # (a stable sort: windows of equal start - two segments of one parent - keep the order of the segments file)
+    order = sorted(range(len(kept)), key=lambda w: (index[kept[w][1]], first[w]))
+    return [kept[w][0] for w in order], [(index[kept[w][1]], first[w], last[w] - first[w] + 1) for w in order], subs
+
+
+def extract_sliding_scp(model, entries, w, opts, batch_frames, batch_utts, max_chunk, verbose=False, ingest=None):
+    """The reference's sliding (diarisation) mode over scp entries: every segment of opts.segments is cut into uniform overlapping
+    sub-segments (libs.amd.subsegments), each a row range of its parent's matrix, and one vector per sub-segment is written under the
+    sub-segment's id.  The reference reads a range-specified scp - the whole parent once per window; here a parent's rows are read and
+    uploaded ONCE per batch that holds windows of it (libs.amd.subsegments.cut_spans: whole parents, or spans of a long one), and
+    asv_ingest_windows builds the batch of windows from the resident rows, CMN per window (DeviceSets.submit_windows).  Plain float32
+    direct entries are read by positioned reads of the spans' rows; compressed direct entries that fit a buffer set travel as their
+    bodies and are decoded on the device (ASV_AMD_DEVICE_DECODE=0: on the host); every other kind is decoded on the host, once per
+    parent.  The loop is extract_stream's: reader thread, three buffer sets, the writer behind the device."""
+    import queue
+    import threading
+    from libs.amd import subsegments
+    from libs.amd.pipeline import DeviceSets, IngestOptions
+    if max_chunk is None:
+        max_chunk = getattr(type(model).extract_embedding, "max_chunk", 10000)
+    if ingest is None:
+        ingest = IngestOptions()                        # --cmn-window 0: the windows' rows as they are
+    refuse_ranged_entries(entries)
+    loader = ScpBatchLoader(entries, threads=_reader_threads())
+    clock = time.perf_counter
+    try:
+        # (the header pass, the windows and the cut are this mode's own host work: counted into the loop's clock below - the
+        #  range-specified scp they replace comes ready-made)
+        t_windows = clock()
+        loader.index_all()
+        lengths = loader.lengths()
+        ids, windows, subs = sliding_windows(entries, lengths, opts)
+        if opts.subsegments_out:
+            with open(opts.subsegments_out, "w") as f:
+                f.write("".join(line + "\n" for line in subsegments.format_subsegments(subs)))
+        if not windows:
+            return 0
+        dim = int(loader.shape(windows[0][0])[1])
+        for p in sorted({win[0] for win in windows}):
+            h = loader._direct(p) or loader._direct_compressed(p)
+            if h is not None and h[3] != dim:
+                raise kaldi_io.BadInputFormat("scp entry '%s' has %d columns, the table started with %d" % (entries[p][0], h[3], dim))
+        device_decode = os.environ.get("ASV_AMD_DEVICE_DECODE", "1") != "0"
+        whole = {p for p in {win[0] for win in windows} if device_decode and loader.compressed_format(p) and lengths[p] <= batch_frames}
+        batches = subsegments.cut_spans(lengths, windows, batch_frames, batch_utts, whole=whole)
+        t_windows = clock() - t_windows
+        sets = DeviceSets(model, batch_frames, batch_utts, dim, max_chunk, n_sets=3, results="host", ingest=ingest, compressed=bool(whole), windows=True)
+        free_sets, staged = queue.Queue(), queue.Queue()
+        for k in range(sets.n_sets):
+            free_sets.put(k)
+
+        def produce():
+            try:
+                for batch in batches:
+                    k = free_sets.get()
+                    w0, w1 = batch.spans[0].w0, batch.spans[-1].w1
+                    if batch.own:                         # one window longer than a whole buffer: an array of its own, submit()'s own path
+                        span = batch.spans[0]
+                        big = np.empty((span.row1 - span.row0, dim), dtype=np.float32)
+                        loader.fill_rows([(span.parent, span.row0, span.row1, 0)], big)
+                        staged.put((k, w0, w1, big, None, None, None))
+                        continue
+                    at, fills, start = 0, [], np.zeros(w1 - w0, dtype=np.int64)
+                    for span in batch.spans:
+                        fills.append((span.parent, span.row0, span.row1, at))
+                        for j in range(span.w0, span.w1):
+                            start[j - w0] = at + windows[j][1] - span.row0
+                        at += span.row1 - span.row0
+                    rows = np.asarray([windows[j][2] for j in range(w0, w1)], dtype=np.int64)
+                    packed = None
+                    if batch.whole:
+                        packed = loader.load_compressed([span.parent for span in batch.spans], sets.byte_buffer(k))
+                    else:
+                        loader.fill_rows(fills, sets.host_buffer(k))
+                    staged.put((k, w0, w1, at, start, rows, packed))
+                staged.put(None)
+            except BaseException as e:                    # surfaces in the consumer
+                staged.put(e)
+
+        spent = {"windows": t_windows, "reader": 0.0, "submit": 0.0, "device": 0.0, "write": 0.0}
+        t = threading.Thread(target=produce, daemon=True)
+        t.start()
+        n_done, in_flight = 0, None
+
+        def finish(item):
+            k, keys = item
+            a = clock()
+            vectors = sets.finish(k)
+            b = clock()
+            if verbose:
+                for key in keys:
+                    print("Process utterance for key {0}".format(key))
+            w.write(kaldi_io.vec_flt_ark_bytes(keys, vectors))
+            free_sets.put(k)
+            spent["device"] += b - a
+            spent["write"] += clock() - b
+            return len(keys)
+
+        t0 = clock()
+        while True:
+            a = clock()
+            item = staged.get()
+            b = clock()
+            spent["reader"] += b - a
+            if isinstance(item, BaseException):
+                raise item
+            if item is None:
+                break
+            k, w0, w1, frames, start, rows, packed = item
+            if start is None:
+                sets.submit(k, np.array([0, frames.shape[0]], dtype=np.int32), frames)
+            else:
+                sets.submit_windows(k, frames, start, rows, packed=packed)
+            spent["submit"] += clock() - b
+            if in_flight is not None:
+                n_done += finish(in_flight)
+            in_flight = (k, ids[w0:w1])
+        if in_flight is not None:
+            n_done += finish(in_flight)
+        t.join()
+        _report_loop("sliding", n_done, t_windows + clock() - t0, sets, spent)
+        return n_done
+    finally:
+        loader.close()
+
+
 def _shard_segment_utts(lengths=None, batch_frames=0, batch_utts=0, row_pad=0):
     """Utterances per rank between two gathers of the sharded path (ASV_AMD_SHARD_SEGMENT, default 4096; 0 = one gather at the very
     end), rounded to whole batches of the mean utterance: a segment's last batch is a partial one, and on a device-bound run (f32x)
@@ -1251,6 +1485,7 @@ def main(argv=None):
             raise RuntimeError("asv-subtools_amd extracts on a ROCm device only (--use-gpu=true); there is no CPU path")
 
         sharded = utils.to_bool(args.sharded)
+        sliding = sliding_options(args)               # (refuses what the sliding mode does not take before anything is set up)
         ingest = ingest_options(args)                 # (refuses --sharded true --vad-scp before anything is set up)
         if sharded:
             import torch.distributed as dist
@@ -1295,7 +1530,11 @@ def main(argv=None):
 
         n_done = 0
         vad = VadTable(args.vad_scp, threads=_reader_threads()) if args.vad_scp else None
-        if sharded:
+        if sliding is not None:
+            with kaldi_io.open_or_fd(args.vectors_wspecifier, "wb") as w:
+                n_done = extract_sliding_scp(model, read_scp(args.feats_rspecifier), w, sliding, args.batch_frames, args.batch_utts, max_chunk, verbose,
+                                             ingest=ingest)
+        elif sharded:
             import torch.distributed as dist
             n_done = run_sharded(args, model, max_chunk, verbose)
             if dist.is_initialized():

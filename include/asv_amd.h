@@ -563,6 +563,20 @@ int asv_select_frames(const float *feats, const unsigned char *voiced, const lon
 int asv_ingest_frames(const float *feats, const unsigned char *voiced, const long long *frame_offsets,
                       const long long *out_offsets, int n_utts, int dim, int cmn_window, int min_window, int center,
                       int norm_vars, float *out, void *stream);
+/* A batch of WINDOWS of rows that are already on the device, each normalised as an utterance of its own (the reference's
+ * sliding / diarisation mode: apply-cmvn-sliding over range-specified scp entries 'file:offset[first:last]').  feats: device
+ * [n_rows][dim], the raw rows of one or several parent matrices, packed; win_start / win_len: host int64 [n_windows]; window w
+ * is rows [win_start[w], win_start[w] + win_len[w]) - windows may overlap, repeat, come in any order and from different
+ * parents, and may be empty (nothing is written for one).  out: device [sum(win_len)][dim]; window w starts at the sum of
+ * the lengths before it.  The result equals, bit for bit, what asv_ingest_frames(voiced = NULL) writes for a packed copy of
+ * the windows (and so asv_cmvn_sliding's); cmn_window <= 0 copies the rows as they are.  There are no voiced flags.
+ * Negative return, and no launch: a null pointer, n_windows < 1, dim < 1, a negative start or length, a window that reaches
+ * beyond n_rows, out overlapping feats, a causal window (center = 0) with min_window outside [1, cmn_window].  The host
+ * arrays are staged by the library as asv_ingest_frames stages its own: no stream synchronisation, the caller's arrays may
+ * be reused on return. */
+int asv_ingest_windows(const float *feats, long long n_rows, const long long *win_start, const long long *win_len,
+                       int n_windows, int dim, int cmn_window, int min_window, int center, int norm_vars, float *out,
+                       void *stream);
 /* Kaldi compressed matrices ('CM ', 'CM2', 'CM3': what make_fbank.sh / make_mfcc.sh write with compress=true) -> packed
  * float32 rows, on the stream in front of asv_ingest_frames / asv_net_extract.  bytes: device, the entries' BODIES as they
  * lie on disk behind their token, each from its 16-byte global header {float min, float range, int32 rows, int32 cols}:
