@@ -190,7 +190,7 @@ SYMBOLS = [
     "asv_plda_llr_matrix", "asv_two_cov_matrix",
     "asv_plda_train", "asv_scatter_f64", "asv_class_scatter_f64",
     "asv_fbank_num_frames", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
-    "asv_ingest_frames", "asv_decode_compressed", "asv_ingest_windows",
+    "asv_ingest_frames", "asv_decode_compressed", "asv_ingest_windows", "asv_desilence_pcm16",
 ]
 
 
@@ -277,6 +277,7 @@ def lib():
     L.asv_ingest_frames.argtypes = [vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp, vp]
     L.asv_ingest_windows.argtypes = [vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp, vp]
     L.asv_decode_compressed.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte), ci, ci, vp, vp]
+    L.asv_desilence_pcm16.argtypes = [vp, C.POINTER(C.c_longlong), ci, ci, C.c_double, vp, C.POINTER(C.c_longlong), vp]
     L.asv_cmvn.argtypes = [vp, C.POINTER(C.c_longlong), ci, ci, ci, ci, C.c_float, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)          # AttributeError here = header/.so mismatch

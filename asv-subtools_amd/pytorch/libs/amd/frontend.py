@@ -116,10 +116,65 @@ def fbank_device(wave, sample_off, mean_norm=False, std_norm=False, eps=1e-10, k
     return feats, frame_off
 
 
-def fbank_packed(waveforms, device=None, **kw):
+def de_silence_host(samples, sample_rate, win_len=0.1, min_eng=50):
+    """The reference's waveform trimming (pytorch/libs/egs/signal_processing.py:13-55 de_silence as processor.py:149-175 de_sil calls
+    it for --de-silence true) for one int16 utterance, in numpy: blocks of n = int(win_len * sample_rate) samples plus one tail block of
+    the rest; a block of m samples is kept iff sum |s_i| > min_eng * m - the integer form of mean(|s / 32768|) > min_eng / 32768, which
+    decides as the reference's float32 mean does while min_eng * m stays well below 2^24; the kept blocks in order.  An
+    utterance in which no block survives is returned whole (processor.py:170-171; the threshold halving of lines 166-169 never changes
+    what an utterance yields, and its carry-over to later utterances of a DataLoader worker is not reproduced).  Returns int16."""
+    x = np.ascontiguousarray(samples)
+    if x.dtype != np.int16 or x.ndim != 1:
+        raise ValueError("de_silence: one 1-D int16 (16-bit PCM) utterance, got %s %s" % (x.dtype, x.shape))
+    n = int(win_len * sample_rate)
+    if n < 1:
+        raise ValueError("de_silence: win_len %r at %r Hz is shorter than one sample" % (win_len, sample_rate))
+    min_eng = float(min_eng)
+    if not (np.isfinite(min_eng) and min_eng >= 0.0):
+        raise ValueError("de_silence: min_eng %r" % (min_eng,))
+    if len(x) == 0:
+        return x
+    starts = np.arange(0, len(x), n)
+    sums = np.add.reduceat(np.abs(x.astype(np.int64)), starts)                 # |-32768| = 32768: not in 16 bits
+    sizes = np.minimum(n, len(x) - starts)
+    keep = sums.astype(np.float64) > min_eng * sizes.astype(np.float64)
+    if not keep.any():
+        return x
+    return x[np.repeat(keep, sizes)]
+
+
+def de_silence_device(wave, sample_off, sample_rate, win_len=0.1, min_eng=50):
+    """de_silence_host for a packed batch of 16-bit PCM on the device (asv_desilence_pcm16), sample for sample.  wave: 1-D int16 CUDA
+    tensor of sample_off[-1] samples, sample_off: int64 numpy [n+1] from 0.  Returns (wave_out - a view of the first out_off[-1] samples of
+    a new tensor -, out_off int64 numpy [n+1]): the pair fbank_device takes.  The call waits for the stream once (the host needs the kept
+    counts).  float32 waves are refused: the integer rule is what pins the parity with the reference."""
+    import torch
+    sample_off = _off(sample_off)
+    n = len(sample_off) - 1
+    if isinstance(wave, torch.Tensor) and wave.dtype != torch.int16:
+        raise ValueError("de_silence_device: 16-bit PCM (int16) only, got %s" % (wave.dtype,))
+    if n < 1 or not isinstance(wave, torch.Tensor) or wave.dim() != 1 or not wave.is_cuda or not wave.is_contiguous() or int(sample_off[-1]) != wave.shape[0]:
+        raise ValueError("de_silence_device: wave must be a contiguous 1-D int16 CUDA tensor of sample_off[-1] samples")
+    if int(sample_off[0]) != 0 or (np.diff(sample_off) < 0).any():
+        raise ValueError("de_silence_device: sample_off must start at 0 and not decrease")
+    win = int(win_len * sample_rate)                                             # signal_processing.py:38
+    if win < 1:
+        raise ValueError("de_silence_device: win_len %r at %r Hz is shorter than one sample" % (win_len, sample_rate))
+    out = torch.empty_like(wave)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    if wave.shape[0] == 0:
+        return out, out_off                                # no sample: no launch (an empty tensor has no address to hand over)
+    with torch.cuda.device(wave.device):
+        capi.check(capi.lib().asv_desilence_pcm16(C.c_void_p(wave.data_ptr()), _i64p(sample_off), n, win, float(min_eng), C.c_void_p(out.data_ptr()),
+                                                  _i64p(out_off), C.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)), "asv_desilence_pcm16")
+    return out[:int(out_off[-1])], out_off
+
+
+def fbank_packed(waveforms, device=None, de_silence=None, **kw):
     """waveforms: list of 1-D float arrays / tensors (host or device), samples in the int16 value range.
     Returns (feats [sum frames, dim] f32 CUDA tensor, frame_offsets int64 numpy [n+1]) - the packed layout
-    asv_net_extract consumes, so features never visit the host."""
+    asv_net_extract consumes, so features never visit the host.  de_silence: {"win_len": seconds, "min_eng": threshold} trims the
+    (int16) waveforms on the device between the upload and the features (de_silence_device, at kw's sample_frequency); None: no trimming."""
     import torch
     if len(waveforms) == 0:
         raise ValueError("fbank: empty batch")
@@ -139,6 +194,11 @@ def fbank_packed(waveforms, device=None, **kw):
         for w, a, b in zip(waveforms, sample_off[:-1], sample_off[1:]):
             hv[a:b] = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
         wave = host.to(dev, non_blocking=True)
+    if de_silence is not None:
+        unknown = set(de_silence) - {"win_len", "min_eng"}
+        if unknown:
+            raise TypeError("fbank: unknown de_silence option(s) %s" % sorted(unknown))
+        wave, sample_off = de_silence_device(wave, sample_off, kw.get("sample_frequency", _DEFAULTS["sample_frequency"]), **de_silence)
     return fbank_device(wave, sample_off, **kw)
 
 

@@ -13,18 +13,29 @@ feature_extraction_conf: {feature_type: fbank|mfcc, kaldi_featset: {...torchaudi
 Where the reference decodes, computes torchaudio features, uploads and embeds one utterance at a time (lines 118-135),
 this script ships 16-bit PCM (half the bytes of float features), and runs front-end + extractor on the device per batch:
     reader threads  wav files -> int16 samples packed in a pinned buffer
-    device          H2D, asv_fbank_pcm16 (+ asv_cmvn), asv_net_extract, D2H
+    device          H2D, (asv_desilence_pcm16,) asv_fbank_pcm16 (+ asv_cmvn), asv_net_extract, D2H
     writer          embeddings -> Kaldi vector ark (same bytes as kaldi_io.write_vec_flt per entry), input order
 and prints "RTF:<device seconds per second of audio>" like the reference (line 138).
 
-Not offered: --data-type shard (tar shards of the training pipeline), --de-silence (host-side waveform trimming of the
-training egs, processor.py:149-175); --data-type kaldi never worked in the reference (egs_online.py:258-259 uses an undefined
-dataset) and is rejected too.  WAV files must be 16-bit PCM; the first channel is used (processor.py:138).
+--de-silence true --amp-th N (what every "online" launcher of the reference passes) trims each waveform as the reference's
+processor.py:149-175 de_sil -> signal_processing.py:13-55 de_silence does: blocks of int(0.1 * sample rate) samples whose mean
+absolute amplitude is not above N (16-bit counts) are dropped, the rest concatenated; an utterance in which no block survives is
+kept whole (processor.py:170-171).  The batch is trimmed on the device between the upload and the features (asv_desilence_pcm16,
+sample for sample what libs.amd.frontend.de_silence_host gives); ASV_AMD_DEVICE_DESILENCE=0 trims in the reader threads on the
+host instead.  Decided deviation: the threshold is N for EVERY utterance.  In the reference the retry of processor.py:166-169
+never changes what an utterance yields (line 168 drops the retry's length, so line 171 puts the whole waveform back), but it
+halves the generator-local threshold for every later utterance of the same DataLoader worker - a function of how utterances
+are dealt to its 2 workers, which is not reproduced.  The RTF line counts the frames after trimming, as the reference's does.
+
+Not offered: --data-type shard (tar shards of the training pipeline); --data-type kaldi never worked in the reference
+(egs_online.py:258-259 uses an undefined dataset) and is rejected too.  WAV files must be 16-bit PCM; the first channel is
+used (processor.py:138).
 """
 
 import argparse
 import os
 import sys
+import time
 import traceback
 import wave
 
@@ -46,7 +57,7 @@ def get_args(argv=None):
     parser.add_argument("--model-blueprint", type=str, default=None, help="A *.py which includes the instance of nnet in this training.")
     parser.add_argument("--model-creation", type=str, default=None, help="A command to create the model class, e.g. Xvector(40,2).")
     parser.add_argument("--data-type", type=str, default="raw", choices=["raw", "shard", "kaldi"], help="raw: wav.scp")
-    parser.add_argument("--de-silence", type=str, default="false", choices=["true", "false"], help="Not offered on this path.")
+    parser.add_argument("--de-silence", type=str, default="false", choices=["true", "false"], help="Drop the silent 0.1 s blocks of every waveform (see --amp-th).")
     parser.add_argument("--amp-th", type=int, default=50, help="De_silence threshold (16bit)")
     parser.add_argument("--max-chunk", type=int, default=10000, help="Select chunk_size of features when extracting xvector")
     parser.add_argument("--feat-config", type=str, default="", help="The config yaml of feat extraction")
@@ -71,8 +82,27 @@ def read_wav_pcm16(path):
     return (data.reshape(-1, ch)[:, 0] if ch > 1 else data), sr
 
 
-def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, batch_utts=512, num_readers=4):
-    """items: [(key, wav path)].  Returns (number written, device seconds, audio seconds as frames * 0.01 like the reference)."""
+def check_args(args):
+    """The refusals of the command line that need no device; returns the de-silence threshold (--amp-th) or None (--de-silence false)."""
+    if not utils.to_bool(args.use_gpu):
+        raise RuntimeError("asv-subtools_amd extracts on a ROCm device only (--use-gpu=true); there is no CPU path")
+    if args.data_type != "raw":
+        raise ValueError("Do not support datatype: {0} now.".format(args.data_type))
+    if not utils.to_bool(args.de_silence):
+        return None
+    if args.amp_th < 0:
+        raise ValueError("--amp-th must not be negative: {0}".format(args.amp_th))
+    return args.amp_th
+
+
+def device_desilence():
+    """ASV_AMD_DEVICE_DESILENCE=0: --de-silence trims in the reader threads on the host (frontend.de_silence_host), not on the device."""
+    return os.environ.get("ASV_AMD_DEVICE_DESILENCE", "1") != "0"
+
+
+def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, batch_utts=512, num_readers=4, amp_th=None):
+    """items: [(key, wav path)].  amp_th: the de-silence threshold, None: no trimming.  Returns (number written, device seconds, audio
+    seconds as frames * 0.01 like the reference)."""
     import queue
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -84,6 +114,12 @@ def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, ba
     std_norm = bool(mv.get("std_norm", False)) if mv is not None else False
     dev = torch.device("cuda", engine.device_index)
     batches = queue.Queue(maxsize=2)
+    trim_device = amp_th is not None and device_desilence()
+    read = read_wav_pcm16
+    if amp_th is not None and not trim_device:
+        def read(path):
+            wav, sr = read_wav_pcm16(path)
+            return frontend.de_silence_host(wav, sr, min_eng=amp_th), sr
 
     free_bufs = queue.Queue()                    # two pinned staging buffers rotate between the producer and the consumer
     for _ in range(2):
@@ -99,7 +135,7 @@ def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, ba
                     # decode ahead until the pending audio certainly fills one batch (or the list ends)
                     while pos < len(items) and (len(pending) < batch_utts and sum(len(wv) / float(sr) for _, wv, sr in pending) <= batch_seconds):
                         group = items[pos:pos + max(8, num_readers * 4)]
-                        for (key, _), (wav, sr) in zip(group, pool.map(lambda it: read_wav_pcm16(it[1]), group)):
+                        for (key, _), (wav, sr) in zip(group, pool.map(lambda it: read(it[1]), group)):
                             pending.append((key, wav, sr))
                         pos += len(group)
                     # cut at the audio budget / utterance cap (at least one utterance)
@@ -142,6 +178,8 @@ def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, ba
             torch.cuda.current_stream(dev).synchronize()             # the upload has read the pinned buffer: hand it back
             free_bufs.put(host)
             e0.record()
+            if trim_device:
+                wave_dev, off = frontend.de_silence_device(wave_dev, off, sr, min_eng=amp_th)
             feats, frame_off = frontend.fbank_device(wave_dev, off, kind=kind, mean_norm=mean_norm, std_norm=std_norm,
                                                      **dict(featset, sample_frequency=float(sr)))    # processor.py:428
             keep = [i for i in range(len(keys)) if frame_off[i + 1] > frame_off[i]]
@@ -179,12 +217,7 @@ def main(argv=None):
             model_blueprint, model_creation = args.model_blueprint, args.model_creation
         else:
             raise ValueError("Expected nnet_config or (model_blueprint, model_creation) to exist.")
-        if not utils.to_bool(args.use_gpu):
-            raise RuntimeError("asv-subtools_amd extracts on a ROCm device only (--use-gpu=true); there is no CPU path")
-        if args.data_type != "raw":
-            raise ValueError("Do not support datatype: {0} now.".format(args.data_type))
-        if utils.to_bool(args.de_silence):
-            raise ValueError("--de-silence is not offered by the device path")
+        amp_th = check_args(args)
         with open(args.feat_config, "r") as fin:
             feat_conf = yaml.load(fin, Loader=yaml.FullLoader) or {}
 
@@ -200,8 +233,14 @@ def main(argv=None):
                     continue
                 assert len(arr) == 2, "wav.scp lines are 'utt-id path.wav' (pipes are not supported): %r" % line
                 items.append((arr[0], arr[1]))
+        t0 = time.perf_counter()
         with kaldi_io.open_or_fd(args.vectors_wspecifier, "wb") as w:
-            n_done, dev_s, audio_s = extract_wavs(model, items, w, feat_conf, args.max_chunk, args.batch_seconds, args.batch_utts, args.num_readers)
+            n_done, dev_s, audio_s = extract_wavs(model, items, w, feat_conf, args.max_chunk, args.batch_seconds, args.batch_utts, args.num_readers, amp_th=amp_th)
+        loop_s = time.perf_counter() - t0
+        if os.environ.get("ASV_AMD_REPORT_TIMING", "0") not in ("0", "", "false"):
+            # the read -> device -> write loop alone (model load and start-up excluded), and the device clock the RTF line divides
+            print("Loop: {0} utterances in {1:.4f} s = {2:.1f} utterances/s, device {3:.4f} s, {4:.2f} s of audio".format(
+                n_done, loop_s, n_done / loop_s if loop_s > 0 else 0.0, dev_s, audio_s))
         print("Extracted {0} embeddings.".format(n_done))
         print("RTF:{:.7f}".format(dev_s / audio_s if audio_s > 0 else 0.0))
     except BaseException as e:

@@ -592,6 +592,21 @@ int asv_ingest_windows(const float *feats, long long n_rows, const long long *wi
  * stream synchronisation, the caller's arrays may be reused on return. */
 int asv_decode_compressed(const unsigned char *bytes, const long long *byte_offsets, const long long *frame_offsets,
                           const unsigned char *formats, int n_utts, int dim, float *out, void *stream);
+/* processor.py:149-175 / signal_processing.py:13-55 on 16-bit PCM in HBM, in front of asv_fbank_pcm16: the reference's
+ * --de-silence waveform trimming.  An utterance of L samples is cut into L / win_samples full blocks and, if any samples
+ * remain, one tail block of them; a block of m samples is kept iff sum |s_i| > min_eng * m (the sum an exact integer,
+ * |-32768| = 32768; the product in double) - the reference's mean(|s / 32768|) > min_eng / 32768; the kept blocks are
+ * concatenated in order, and an utterance in which no block is kept (an empty one included) is kept whole.  wave: device,
+ * utterance u = samples [sample_offsets[u], sample_offsets[u+1]) (host int64 [n_utts+1] from 0), any 2-byte alignment;
+ * out: device, capacity sample_offsets[n_utts] samples, must not overlap wave; utterance u of out is [out_offsets[u],
+ * out_offsets[u+1]), packed back to back - the layout asv_fbank_pcm16 takes as sample_offsets - and nothing behind
+ * out_offsets[n_utts] is written.  out_offsets: HOST int64 [n_utts+1], filled before returning: the call waits for the
+ * stream once to hand the kept counts to the host, the same contract as asv_vad_energy's voiced_counts.  The host array
+ * sample_offsets is staged by the library as asv_ingest_frames stages its own: it may be reused on return.  An
+ * utterance's output does not depend on its batch neighbours.  Negative return, and no launch: a null pointer, n_utts < 1,
+ * win_samples < 1, a negative or non-finite min_eng, decreasing offsets, sample_offsets[0] != 0, out overlapping wave. */
+int asv_desilence_pcm16(const short *wave, const long long *sample_offsets, int n_utts, int win_samples, double min_eng,
+                        short *out, long long *out_offsets, void *stream);
 /* Per-utterance mean / variance normalisation of every column, in place (kaldi_features.py:11-66
  * InputSequenceNormalization: mean over the frames, unbiased std floored at eps).  frame_offsets: host int64 [n_utts+1]. */
 int asv_cmvn(float *feats, const long long *frame_offsets, int n_utts, int dim, int mean_norm, int std_norm, float eps,
