@@ -344,6 +344,17 @@ struct EltwiseKernelParams {
 int launch_lde_pool(const void *x, int ldx, int channels, int rows, const float *mu, const float *beta, int n_centres, float *weights,
                     const int32_t *seg_row0, const int32_t *seg_len, int segments, float *out, int ld_out, int et, hipStream_t s);
 int launch_eltwise(const EltwiseKernelParams &p, int et, hipStream_t s);
+// the row op (kernels_rowop.hip, asv_rowop_desc_t): [affine ->] act0 -> [LayerNorm over the `channels` real channels] -> act1 [-> affine]
+constexpr int kRowopMaxChannels = 3072;      // a row lives in one wave's registers: 48 f32 values per lane
+struct RowopKernelParams {
+  const void *in; void *out;           // already offset to their channel views; out == in: in place
+  int ldi, ldo, channels, rows;
+  const float *scale0, *shift0, *gamma, *beta, *scale1, *shift1;     // [round_up(channels, kChanAlign)] each, or nullptr
+  int act0, act1, ln;
+  float slope0, slope1, eps;
+  const uint32_t *row_valid;           // nullptr in the utts domain
+};
+int launch_rowop(const RowopKernelParams &p, int et, hipStream_t s);
 
 // float64 score matrices of the PLDA back-end (kernels_score_matrix.hip): C[i][j] = sum_k A[i][k] B[j][k] + row[i] + col[j] on the f64
 // matrix instruction.  A [m][kp], B [n][kp] float64 with kp a multiple of kScoreMatrixKChunk and zeros beyond the real K (the

@@ -156,7 +156,7 @@ struct Domain {
   int gap() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : pitch + 2; }
 };
 
-enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10 };
+enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10, OP_ROWOP = 11 };
 
 struct Op {
   OpKind kind;
@@ -172,6 +172,7 @@ struct Op {
   asv_mq_attpool_desc_t mq;
   asv_res2n_desc_t res2n;        // likewise (bias stays nullptr when the op has none)
   asv_res2_desc_t res2;          // fragments in `wfrag`, per-branch constants in bias / scale / shift
+  asv_rowop_desc_t rop;          // host pointers nulled; the per-channel tables live in `rop_tab`
   // device parameters
   void *w = nullptr;
   void *wfrag = nullptr;         // fragment-ordered copy for the variant-3 kernel (bf16 frame layers); pooled layers: bf16 hi halves
@@ -180,6 +181,7 @@ struct Op {
   void *wx3p = nullptr;          // f32x mode, wide frame layers with the plain epilogue: [hi | lo] rows for kernels_tdnn_p8x.hip
   void *w8 = nullptr, *w8_fold = nullptr;      // f32m form (ASV_FLAG_X3_MX8): 8-bit fragments of the layer / of its folded weights (pack_tdnn_weight_mx8)
   float *bias = nullptr, *scale = nullptr, *shift = nullptr;
+  float *rop_tab[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // row op: scale0, shift0, gamma, beta, scale1, shift1
   int cin_pad = 0, cout_pad = 0, cout_store = 0;
   // chain candidates (16-bit modes, 1-tap layers reading a 512-channel buffer): host copies kept until asv_net_finalize, which
   // folds the eval BatchNorm of the PREVIOUS chain layer into this layer's weights and bias (see the chain pass there)
@@ -203,8 +205,8 @@ struct DevMem {
   size_t cap = 0;
 };
 
-const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain"};
-enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
+const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain", "rowop"};
+enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_ROWOP, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
 
 }  // namespace
 }  // namespace asv
@@ -261,7 +263,7 @@ struct asv_net {
 
 namespace {
 
-std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_RES2N + 1];       // asv_kernel_launch_count (ids start at 1)
+std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_ROWOP + 1];       // asv_kernel_launch_count (ids start at 1)
 
 // the range-status word of the f32x kernels lives behind the zero page's zeros (own 64-byte line; kernels only ever OR into it)
 uint32_t *status_word(asv_net *net) { return reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(net->zero_page) + 128); }
@@ -859,6 +861,36 @@ int asv_net_add_eltwise(asv_net_t *net, const asv_eltwise_desc_t *d) {
   return ASV_OK;
 }
 
+int asv_net_add_rowop(asv_net_t *net, const asv_rowop_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_rowop: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_rowop_desc_t), "asv_net_add_rowop: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(asv_rowop_desc_t));
+  for (int a : {d->act0, d->act1}) ASV_REQUIRE(a >= ASV_ACT_NONE && a <= ASV_ACT_DOUBLE_SWISH, "rowop: unknown activation %d", a);
+  int rc;
+  if ((rc = check_view(net, d->in_buf, d->in_ch_off, d->channels, "rowop input"))) return rc;
+  if ((rc = check_view(net, d->out_buf, d->out_ch_off, d->channels, "rowop output"))) return rc;
+  const int dom = net->bufs[d->in_buf].domain;
+  ASV_REQUIRE(net->is_utts(dom) || net->is_sequence(dom), "rowop: grid domains are not supported (frames, sequence and utts domains only)");
+  ASV_REQUIRE(net->bufs[d->out_buf].domain == dom && d->out_buf != 0, "rowop: bad output buffer (the input's domain, never the feature buffer)");
+  ASV_REQUIRE(d->channels <= kRowopMaxChannels, "rowop: %d channels (at most %d: a row lives in one wave's registers)", d->channels, kRowopMaxChannels);
+  const int vec = net->dom_et(dom) != ET_F32 ? 8 : 4;
+  ASV_REQUIRE(d->in_ch_off + round_up(d->channels, vec) <= net->bufs[d->in_buf].ld && d->out_ch_off + round_up(d->channels, vec) <= net->bufs[d->out_buf].ld,
+              "rowop: padded view exceeds pitch");
+  ASV_REQUIRE(d->in_buf != d->out_buf || d->in_ch_off == d->out_ch_off || d->in_ch_off + round_up(d->channels, kChanAlign) <= d->out_ch_off ||
+              d->out_ch_off + round_up(d->channels, kChanAlign) <= d->in_ch_off, "rowop: the output view overlaps the input view without being it (in place: the same offset)");
+  ASV_REQUIRE((d->scale0 == nullptr) == (d->shift0 == nullptr) && (d->scale1 == nullptr) == (d->shift1 == nullptr), "rowop: scale and shift come together");
+  ASV_REQUIRE((d->gamma == nullptr) == (d->beta == nullptr), "rowop: gamma and beta come together");
+  ASV_REQUIRE(d->gamma == nullptr || d->ln, "rowop: gamma / beta without ln");
+  ASV_REQUIRE(!d->ln || (d->eps > 0.0f && std::isfinite(d->eps)), "rowop: ln needs a positive eps (got %g)", (double)d->eps);
+  Op op; op.kind = OP_ROWOP; op.rop = *d; op.utts = net->is_utts(dom);
+  ASV_ON_DEVICE(net->device);
+  const float *tabs[6] = {d->scale0, d->shift0, d->gamma, d->beta, d->scale1, d->shift1};
+  for (int k = 0; k < 6; ++k)
+    if (tabs[k] != nullptr && (rc = upload_padded(net, tabs[k], d->channels, round_up(d->channels, kChanAlign), 0.0f, &op.rop_tab[k]))) return rc;
+  op.rop.scale0 = op.rop.shift0 = op.rop.gamma = op.rop.beta = op.rop.scale1 = op.rop.shift1 = nullptr;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
 int asv_net_add_grid_input(asv_net_t *net, const asv_grid_input_desc_t *d) {
   ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_grid_input: net is null or finalized");
   ASV_REQUIRE(d->struct_size == sizeof(asv_grid_input_desc_t), "asv_net_add_grid_input: struct_size mismatch");
@@ -944,7 +976,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                              o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.x_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.logit_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
-                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
+                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1};
         for (int rbuf : reads) other_reader |= (rbuf == d.out_buf);
       }
       if (other_reader || d.out_buf == out_buf) continue;
@@ -963,7 +995,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                            o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                            o.kind == OP_ELTWISE ? o.elt.seg_scale_buf : -1, o.kind == OP_ELTWISE ? o.elt.seg_norm_buf : -1, o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
                            o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_IM2COL ? o.i2c.seg_scale_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_GRID_INPUT ? o.gin.in_buf : -1,
-                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1};
+                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1};
       for (int rbuf : reads) if (rbuf == buf) return false;
     }
     return true;
@@ -1099,7 +1131,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream) {
 }
 
 unsigned long long asv_kernel_launch_count(int which) {
-  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_RES2N) ? g_kernel_launches[which].load() : 0ull;
+  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_ROWOP) ? g_kernel_launches[which].load() : 0ull;
 }
 
 size_t asv_net_device_bytes(const asv_net_t *net) {
@@ -1172,6 +1204,11 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
       case OP_ELTWISE:
         snprintf(line, sizeof(line), "  op %zu: eltwise a=%d b=%d c=%d segscale=%d affine=%d channels=%d -> %d[%d]%s\n", i, op.elt.a_buf, op.elt.b_buf, op.elt.c_buf,
                  op.elt.seg_scale_buf, op.scale != nullptr, op.elt.channels, op.elt.out_buf, op.elt.out_ch_off, op.elt.out2_buf >= 0 ? " (+ second output)" : "");
+        break;
+      case OP_ROWOP:
+        snprintf(line, sizeof(line), "  op %zu: rowop %d[%d:+%d] -> %d[%d] affine0=%d act0=%d ln=%d(affine=%d eps=%g) act1=%d affine1=%d\n", i, op.rop.in_buf, op.rop.in_ch_off,
+                 op.rop.channels, op.rop.out_buf, op.rop.out_ch_off, op.rop_tab[0] != nullptr, op.rop.act0, op.rop.ln, op.rop_tab[2] != nullptr, (double)op.rop.eps,
+                 op.rop.act1, op.rop_tab[4] != nullptr);
         break;
     }
     s += line;
@@ -1829,6 +1866,25 @@ int run_ops(RunCtx &c, size_t n_ops) {
         if ((rc = prof.end())) return rc;
         break;
       }
+      case OP_ROWOP: {
+        const auto &d = op.rop;
+        const int domid = net->bufs[d.in_buf].domain;
+        ASV_REQUIRE(!c.buf_image[d.in_buf], "rowop: image rows reached the row op (internal)");
+        RowopKernelParams p;
+        memset(&p, 0, sizeof(p));
+        p.in = view(c, d.in_buf, d.in_ch_off); p.ldi = net->bufs[d.in_buf].ld;
+        p.out = view(c, d.out_buf, d.out_ch_off); p.ldo = net->bufs[d.out_buf].ld;
+        p.channels = d.channels;
+        p.scale0 = op.rop_tab[0]; p.shift0 = op.rop_tab[1]; p.gamma = op.rop_tab[2]; p.beta = op.rop_tab[3]; p.scale1 = op.rop_tab[4]; p.shift1 = op.rop_tab[5];
+        p.act0 = d.act0; p.act1 = d.act1; p.ln = d.ln; p.slope0 = d.slope0; p.slope1 = d.slope1; p.eps = d.eps;
+        if (op.utts) { p.rows = bp.segments; }
+        else { p.rows = c.dom[domid].rows_pad; p.row_valid = c.dom[domid].row_valid; }
+        if ((rc = prof.begin(K_ROWOP, 0, (int)i))) return rc;
+        if ((rc = launch_rowop(p, net->dom_et(domid), c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_ROWOP];
+        if ((rc = prof.end())) return rc;
+        break;
+      }
       case OP_RES2: {
         const auto &d = op.res2;
         const DomainRun &dr = c.dom[ASV_DOMAIN_FRAMES];
@@ -2012,6 +2068,56 @@ int asv_stats_pool_forward(const float *x, int channels, const int32_t *offsets,
   if ((rc = pack_features(c, x))) return rc;
   if ((rc = run_ops(c, 1))) return rc;
   ASV_HIP_CHECK(hipMemcpy2DAsync(y, (size_t)out_ch * 4, net->arena[ob].ptr, (size_t)net->bufs[ob].ld * 4, (size_t)out_ch * 4, n_utts, hipMemcpyDeviceToDevice, c.s));
+  ASV_HIP_CHECK(hipStreamSynchronize(c.s));
+  return ASV_OK;
+}
+
+int asv_rowop_forward(const asv_rowop_desc_t *d, int precision, int domain, int width, const float *x, const int32_t *offsets, int n_utts, float *y,
+                      void *stream) {
+  ASV_REQUIRE(d && x && y && offsets && width >= 1 && n_utts >= 1, "asv_rowop_forward: bad argument");
+  ASV_REQUIRE(domain == ASV_DOMAIN_FRAMES || domain == ASV_DOMAIN_UTTS, "asv_rowop_forward: domain %d (frames or utts)", domain);
+  const bool utts = domain == ASV_DOMAIN_UTTS;
+  if (utts)
+    for (int u = 0; u < n_utts; ++u) ASV_REQUIRE(offsets[u + 1] - offsets[u] == 1, "asv_rowop_forward: utts domain: utterance %d must be one frame long", u);
+  int dev = 0;
+  ASV_HIP_CHECK(hipGetDevice(&dev));
+  asv_net_t *net = nullptr;
+  int rc = asv_net_create(&net, dev, precision, 0, width);
+  if (rc) return rc;
+  std::unique_ptr<asv_net_t, void (*)(asv_net_t *)> guard(net, asv_net_destroy);
+  // buffer 1 (and 2, unless the op runs in place) = the rows themselves: a copy in the frames domain, the mean of each one-frame
+  // utterance - the frame, exactly - in the utts domain
+  const int n_bufs = d->out_buf == 1 ? 1 : 2;
+  for (int b = 1; b <= n_bufs; ++b) {
+    const int id = asv_net_new_buffer(net, domain, width);
+    if (id < 0) return id;
+    if (utts) {
+      asv_pool_desc_t pd;
+      memset(&pd, 0, sizeof(pd));
+      pd.struct_size = sizeof(pd); pd.in_buf = 0; pd.channels = width; pd.out_buf = id; pd.eps = 1e-10f;
+      if ((rc = asv_net_add_stats_pool(net, &pd))) return rc;
+    } else {
+      asv_eltwise_desc_t ed;
+      memset(&ed, 0, sizeof(ed));
+      ed.struct_size = sizeof(ed); ed.channels = width; ed.a_buf = 0; ed.b_buf = ed.c_buf = ed.seg_scale_buf = ed.seg_norm_buf = ed.d_buf = ed.out2_buf = -1; ed.out_buf = id;
+      if ((rc = asv_net_add_eltwise(net, &ed))) return rc;
+    }
+  }
+  asv_rowop_desc_t dd = *d;
+  dd.in_buf = 1; dd.out_buf = n_bufs;
+  if ((rc = asv_net_add_rowop(net, &dd))) return rc;
+  net->arena.resize(net->bufs.size());
+  RunCtx c;
+  c.net = net; c.s = reinterpret_cast<hipStream_t>(stream);
+  if ((rc = prepare(c, offsets, n_utts, 1 << 30))) return rc;
+  if ((rc = pack_features(c, x))) return rc;
+  if ((rc = run_ops(c, net->ops.size()))) return rc;
+  if (utts) {
+    ASV_HIP_CHECK(hipMemcpy2DAsync(y, (size_t)width * 4, net->arena[n_bufs].ptr, (size_t)net->bufs[n_bufs].ld * 4, (size_t)width * 4, n_utts, hipMemcpyDeviceToDevice, c.s));
+  } else {
+    const DomainRun &dr = c.dom[ASV_DOMAIN_FRAMES];
+    if ((rc = launch_unpack_rows(net->arena[n_bufs].ptr, net->bufs[n_bufs].ld, width, c.seg_src0, dr.seg_row0, dr.row_seg, dr.rows_pad, y, net->frames_et(), c.s))) return rc;
+  }
   ASV_HIP_CHECK(hipStreamSynchronize(c.s));
   return ASV_OK;
 }

@@ -15,6 +15,7 @@ PREC_F32, PREC_BF16, PREC_F32X, PREC_F16 = 0, 1, 2, 3
 FLAG_REF_KERNELS, FLAG_NO_FUSE, FLAG_SMALL_TILES, FLAG_BIG_V2, FLAG_NO_CHAIN = 1, 2, 4, 8, 16
 FLAG_X3_SPLIT_BF16, FLAG_X3_SPLIT_F16, FLAG_X3_NO_XLO, FLAG_X3_NO_WLO, FLAG_X3_TILE128, FLAG_X3_MX8 = 32, 64, 128, 256, 512, 1024
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
+ACT_LEAKY_RELU, ACT_SELU, ACT_MISH, ACT_SWISH, ACT_GELU, ACT_DOUBLE_SWISH = 4, 5, 6, 7, 8, 9      # the row op's (asv_net_add_rowop only)
 DOMAIN_FRAMES, DOMAIN_UTTS = 0, 1
 MAX_TAPS = 9
 POOL_VAR_CLAMP, POOL_VAR_ADD = 0, 1
@@ -24,10 +25,12 @@ KERNEL_TDNN_P8, KERNEL_TDNN_BIG3, KERNEL_TDNN_P8X, KERNEL_TDNN_CHAINM, KERNEL_TD
 KERNEL_MQ_ATTPOOL = 7
 KERNEL_CONV_C1, KERNEL_CONV_NARROW, KERNEL_CONV_NARROW_PERS, KERNEL_CONV_WIDE, KERNEL_CONV_S2D = 8, 9, 10, 11, 12
 KERNEL_RES2N = 13
+KERNEL_ROWOP = 14
 RES2N_TILE_ROWS = 192          # ASV_RES2N_TILE_ROWS: rows a workgroup of res2n_chain_kernel produces
 
 ACT_BY_NAME = {None: ACT_NONE, "": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
+ROWOP_ACT_BY_NAME = dict(ACT_BY_NAME, leaky_relu=ACT_LEAKY_RELU, selu=ACT_SELU, mish=ACT_MISH, swish=ACT_SWISH, gelu=ACT_GELU, double_swish=ACT_DOUBLE_SWISH)
 
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -133,6 +136,21 @@ class EltwiseDesc(C.Structure):
     ]
 
 
+class RowopDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("channels", C.c_int32),
+        ("in_buf", C.c_int32), ("in_ch_off", C.c_int32), ("out_buf", C.c_int32), ("out_ch_off", C.c_int32),
+        ("act0", C.c_int32), ("act1", C.c_int32),
+        ("slope0", C.c_float), ("slope1", C.c_float),
+        ("ln", C.c_int32),
+        ("eps", C.c_float),
+        ("scale0", c_float_p), ("shift0", c_float_p),
+        ("gamma", c_float_p), ("beta", c_float_p),
+        ("scale1", c_float_p), ("shift1", c_float_p),
+    ]
+
+
 class GridInputDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("out_buf", C.c_int32), ("in_buf", C.c_int32)]
 
@@ -181,10 +199,10 @@ SYMBOLS = [
     "asv_version", "asv_last_error", "asv_device_count",
     "asv_net_create", "asv_net_destroy", "asv_net_define_grid", "asv_net_new_buffer", "asv_net_add_tdnn",
     "asv_net_add_grid_input", "asv_net_add_im2col", "asv_net_add_grid_flatten",
-    "asv_net_add_stats_pool", "asv_net_add_attentive_pool", "asv_net_add_mq_attentive_pool", "asv_net_add_lde_pool", "asv_net_add_eltwise", "asv_net_add_res2", "asv_net_add_res2n",
+    "asv_net_add_stats_pool", "asv_net_add_attentive_pool", "asv_net_add_mq_attentive_pool", "asv_net_add_lde_pool", "asv_net_add_eltwise", "asv_net_add_rowop", "asv_net_add_res2", "asv_net_add_res2n",
     "asv_net_finalize", "asv_net_embed_dim", "asv_net_describe", "asv_net_extract",
     "asv_net_device_bytes", "asv_net_set_profiling", "asv_net_get_profile", "asv_net_status", "asv_net_status_async", "asv_kernel_launch_count",
-    "asv_tdnn_forward", "asv_stats_pool_forward",
+    "asv_tdnn_forward", "asv_stats_pool_forward", "asv_rowop_forward",
     "asv_length_norm", "asv_mean_vec", "asv_dot_score_matrix", "asv_dot_score_trials",
     "asv_plda_transform", "asv_plda_llr_trials", "asv_eer", "asv_det_curve", "asv_min_dcf", "asv_cavg", "asv_score_norm", "asv_group_mean", "asv_two_cov_trials",
     "asv_plda_llr_matrix", "asv_two_cov_matrix",
@@ -233,6 +251,7 @@ def lib():
     L.asv_net_add_mq_attentive_pool.argtypes = [vp, C.POINTER(MqAttPoolDesc)]
     L.asv_net_add_lde_pool.argtypes = [vp, C.POINTER(LdeDesc)]
     L.asv_net_add_eltwise.argtypes = [vp, C.POINTER(EltwiseDesc)]
+    L.asv_net_add_rowop.argtypes = [vp, C.POINTER(RowopDesc)]
     L.asv_net_add_res2.argtypes = [vp, C.POINTER(Res2Desc)]
     L.asv_net_add_res2n.argtypes = [vp, C.POINTER(Res2nDesc)]
     L.asv_net_finalize.argtypes = [vp, ci, ci]
@@ -247,6 +266,7 @@ def lib():
     L.asv_net_get_profile.argtypes = [vp, C.POINTER(KernelTime), ci, C.POINTER(ci)]
     L.asv_tdnn_forward.argtypes = [C.POINTER(TdnnDesc), ci, cu, vp, c_int32_p, ci, vp, vp]
     L.asv_stats_pool_forward.argtypes = [vp, ci, c_int32_p, ci, ci, ci, ci, C.c_float, vp, vp]
+    L.asv_rowop_forward.argtypes = [C.POINTER(RowopDesc), ci, ci, ci, vp, c_int32_p, ci, vp, vp]
     L.asv_length_norm.argtypes = [vp, ci, ci, vp, ci, vp]
     L.asv_mean_vec.argtypes = [vp, ci, ci, vp, vp]
     L.asv_dot_score_matrix.argtypes = [vp, ci, vp, ci, ci, vp, vp]

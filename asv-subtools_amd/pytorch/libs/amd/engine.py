@@ -249,6 +249,12 @@ class Engine(object):
                 d.d_buf, d.d_ch_off = bv(getattr(op, "d", None))
                 d.out2_buf, d.out2_ch_off = bv(getattr(op, "out2", None))
                 capi.check(L.asv_net_add_eltwise(self._net, C.byref(d)), "asv_net_add_eltwise")
+            elif op.kind == "rowop":
+                d, keep = self._rowop_desc(op)
+                d.in_buf, d.in_ch_off = bv(op.inp)
+                d.out_buf, d.out_ch_off = bv(op.out)
+                capi.check(L.asv_net_add_rowop(self._net, C.byref(d)), "asv_net_add_rowop")
+                del keep
             elif op.kind == "grid_input":
                 d = capi.GridInputDesc()
                 d.struct_size = C.sizeof(capi.GridInputDesc)
@@ -276,6 +282,23 @@ class Engine(object):
         if g.output.ch_off != 0:
             raise _ir.TraceError("the embedding must start at channel 0 of its buffer")
         capi.check(L.asv_net_finalize(self._net, buf_of[g.output.tid], g.output.channels), "asv_net_finalize")
+
+    @staticmethod
+    def _rowop_desc(op):
+        """ir 'rowop' op -> (capi.RowopDesc without its buffer views, the arrays its pointers borrow)."""
+        d = capi.RowopDesc()
+        d.struct_size = C.sizeof(capi.RowopDesc)
+        d.channels = op.inp.channels
+        d.act0, d.act1 = capi.ROWOP_ACT_BY_NAME[op.act0], capi.ROWOP_ACT_BY_NAME[op.act1]
+        d.slope0, d.slope1 = op.slope0, op.slope1
+        d.ln, d.eps = int(op.ln), op.eps
+        keep = []
+        for name in ("scale0", "shift0", "gamma", "beta", "scale1", "shift1"):
+            a = getattr(op, name)
+            if a is not None:
+                keep.append(a)
+                setattr(d, name, capi.f32_ptr(a))
+        return d, keep
 
     def close(self):
         twin = getattr(self, "_wide_range_twin", None)

@@ -48,7 +48,7 @@ class View(object):
 
 
 class Op(object):
-    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','cat','grid_input','im2col'}; `out` is a View covering
+    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','rowop','cat','grid_input','im2col'}; `out` is a View covering
     a whole tensor until concat elision redirects it into a slice of a wider one."""
 
     def __init__(self, kind, out, **attrs):
@@ -68,7 +68,7 @@ class Op(object):
             names = ("a", "b", "c", "seg_scale", "seg_norm", "d")
         elif self.kind == "im2col":
             names = ("inp", "b", "seg_scale")
-        elif self.kind in ("grid_input", "res2", "res2n", "flatten"):
+        elif self.kind in ("grid_input", "res2", "res2n", "flatten", "rowop"):
             names = ("inp",)
         else:
             return list(self.parts)
@@ -77,7 +77,7 @@ class Op(object):
     def input_names(self):
         return {"tdnn": ("inp", "inp2", "seg_bias", "seg_scale", "res"), "pool": ("inp",),
                 "attpool": ("x", "logits"), "mqattpool": ("x", "logits"), "lde": ("x",), "eltwise": ("a", "b", "c", "seg_scale", "seg_norm", "d"), "cat": (), "grid_input": ("inp",),
-                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",)}[self.kind]
+                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",), "rowop": ("inp",)}[self.kind]
 
 
 class Graph(object):
@@ -217,6 +217,21 @@ class Graph(object):
         f32 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float32)
         self.ops.append(Op("eltwise", out, a=a, b=b, c=c, seg_scale=seg_scale, scale=f32(scale), shift=f32(shift), act=act or None,
                            seg_norm=seg_norm, seg_norm_mode=int(seg_norm_mode)))
+        return out
+
+    def rowop(self, inp, act0=None, slope0=0.01, ln=False, eps=1e-5, gamma=None, beta=None, act1=None, slope1=0.01,
+              scale0=None, shift0=None, scale1=None, shift1=None):
+        """The row op (asv_rowop_desc_t, kernels_rowop.hip): z = inp * scale0 + shift0; z = act0(z); LayerNorm over the channels
+        (biased variance, eps, optional gamma / beta); z = act1(z); z * scale1 + shift1 - every step optional.  Frames, sequence
+        and utts tensors.  No graph pass looks inside it or merges its neighbours through it."""
+        if self.grid_spec(inp.tid) is not None:
+            raise TraceError("the row op (activations beyond relu / tanh / sigmoid, LayerNorm) does not run on a 2-D grid tensor")
+        if (gamma is None) != (beta is None) or (gamma is not None and not ln):
+            raise TraceError("rowop: gamma and beta come together, with ln")
+        out = self.full_view(self.new_tensor(self.domain(inp.tid), inp.channels))
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+        self.ops.append(Op("rowop", out, inp=inp, act0=act0 or None, slope0=float(slope0), ln=bool(ln), eps=float(eps), gamma=f32(gamma), beta=f32(beta),
+                           act1=act1 or None, slope1=float(slope1), scale0=f32(scale0), shift0=f32(shift0), scale1=f32(scale1), shift1=f32(shift1)))
         return out
 
     def cat(self, parts, align=1):
@@ -629,6 +644,10 @@ class Graph(object):
                 ins, extra = "x=%r logits=%r" % (op.x, op.logits), "heads=%d queries=%d shared=%s eps=%g" % (op.heads, op.queries, op.shared, op.eps)
             elif op.kind == "lde":
                 ins, extra = "x=%r" % (op.x,), "centres=%d" % len(op.beta)
+            elif op.kind == "rowop":
+                ins = repr(op.inp)
+                extra = "affine0=%s act0=%s ln=%s%s act1=%s affine1=%s" % (op.scale0 is not None, op.act0, op.ln, "(affine)" if op.gamma is not None else "",
+                                                                           op.act1, op.scale1 is not None)
             elif op.kind == "eltwise":
                 ins = " ".join("%s=%r" % (n, getattr(op, n)) for n in ("a", "b", "c", "seg_scale") if getattr(op, n) is not None)
                 extra = "affine=%s act=%s" % (op.scale is not None, op.act)

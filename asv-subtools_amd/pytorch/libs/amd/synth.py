@@ -40,7 +40,8 @@ def synth_tensor(key, shape, seed=0):
         return (0.5 * r.standard_normal(shape)).astype(np.float32)
     if leaf == "running_var":
         return r.uniform(0.5, 2.0, shape).astype(np.float32)
-    if leaf == "weight" and len(shape) == 1:           # BN gamma
+    if leaf == "weight" and len(shape) == 1:           # BN gamma - and the gamma of a LayerNorm that stands in for it (`ln_replace`:
+                                                       # batchnorm.weight / batchnorm.bias, no running statistics): never the 1 / 0 of the initialisation
         return r.uniform(0.5, 1.5, shape).astype(np.float32)
     if leaf == "bias":
         return (0.2 * r.standard_normal(shape)).astype(np.float32)

@@ -15,7 +15,7 @@ import torch
 
 import libs.support.utils as utils
 from libs.amd import ir as _ir
-from .activation import Nonlinearity, activation_name
+from .activation import Nonlinearity, activation_name, HIP_ACTIVATIONS
 
 
 def _eager_unsupported(name):
@@ -123,8 +123,21 @@ class TdnnAffine(torch.nn.Module):
                 "groups={groups}, norm_w={norm_w}, norm_f={norm_f}".format(**self.__dict__))
 
 
+class LayerNorm(torch.nn.LayerNorm):
+    """LayerNorm over the channels of [B, C, T] (reference libs/nnet/transformer/layer_norm.py:57-79, dim=1): the parameter
+    holder of `ln_replace`, state_dict keys weight / bias, no running statistics.  The row op normalises (kernels_rowop.hip)."""
+
+    def __init__(self, nout, dim=-1, eps=1e-5, learnabel_affine=True):
+        super(LayerNorm, self).__init__(nout, eps=eps, elementwise_affine=learnabel_affine)
+        self.dim = dim
+
+    def forward(self, x):
+        _eager_unsupported("LayerNorm")
+
+
 class _BaseActivationBatchNorm(torch.nn.Module):
-    """[affine ->] activation -> BatchNorm1d ("bn-relu": BatchNorm1d -> activation)."""
+    """[affine ->] activation -> BatchNorm1d ("bn-relu": BatchNorm1d -> activation); with `ln_replace` a LayerNorm over the
+    channels takes the BatchNorm's place (and its attribute name, as in the reference)."""
 
     def __init__(self):
         super(_BaseActivationBatchNorm, self).__init__()
@@ -146,17 +159,21 @@ class _BaseActivationBatchNorm(torch.nn.Module):
             "jit_compile": False,
         }
         p = utils.assign_params_dict(defaults, options)
-        if p["ln_replace"]:
-            raise NotImplementedError("ln_replace (LayerNorm instead of BatchNorm) is not implemented on the MI355X path")
         self.bn_relu = bool(p["bn-relu"])
         # registration order matches the reference so printed models / state_dict order agree
         if not self.bn_relu:
             self.activation = Nonlinearity(p["nonlinearity"], **p["nonlinearity_params"])
             if p["bn"]:
-                self.batchnorm = torch.nn.BatchNorm1d(output_dim, **p["bn_params"])
+                if not p["ln_replace"]:
+                    self.batchnorm = torch.nn.BatchNorm1d(output_dim, **p["bn_params"])
+                else:                       # components.py:376: the elementwise affine follows bn_params["affine"]
+                    self.batchnorm = LayerNorm(output_dim, dim=1, eps=1e-5, learnabel_affine=p["bn_params"]["affine"])
         else:
             if p["bn"]:
-                self.batchnorm = torch.nn.BatchNorm1d(output_dim, **p["bn_params"])
+                if not p["ln_replace"]:
+                    self.batchnorm = torch.nn.BatchNorm1d(output_dim, **p["bn_params"])
+                else:                       # components.py:385: always with its elementwise affine
+                    self.batchnorm = LayerNorm(output_dim, dim=1, eps=1e-5)
             self.activation = Nonlinearity(p["nonlinearity"], **p["nonlinearity_params"])
         if p["special_init"] and self.affine is not None and not p["jit_compile"]:
             if p["nonlinearity"] in ("relu", "leaky_relu", "tanh", "sigmoid"):
@@ -175,11 +192,38 @@ class _BaseActivationBatchNorm(torch.nn.Module):
         return _ir.fold_batchnorm(bn.running_mean.detach().cpu().numpy(), bn.running_var.detach().cpu().numpy(), g, b, bn.eps)
 
     def forward(self, inputs):
-        if isinstance(inputs, _ir.Sym):
+        if not isinstance(inputs, _ir.Sym):
+            _eager_unsupported(type(self).__name__)
+        act = activation_name(self.activation)
+        ln = self.batchnorm if isinstance(self.batchnorm, torch.nn.LayerNorm) else None
+        if act in (None,) + HIP_ACTIVATIONS and ln is None:
+            # everything fits the GEMM epilogue: one fused op
             scale, shift = self.folded_batchnorm()
-            return self.affine.emit(inputs, act1=activation_name(self.activation), scale=scale, shift=shift,
-                                    affine_first=self.bn_relu)
-        _eager_unsupported(type(self).__name__)
+            return self.affine.emit(inputs, act1=act, scale=scale, shift=shift, affine_first=self.bn_relu)
+        # otherwise: the affine with what its epilogue can still do, then the row op (activation / LayerNorm / the rest)
+        if act == "gelu" and getattr(self.activation, "approximate", "none") != "none":
+            raise _ir.TraceError("GELU(approximate=%r): the row op has the exact erf form only" % self.activation.approximate)
+        slope = float(getattr(self.activation, "negative_slope", 0.01))
+        kw = {}
+        if ln is not None:
+            kw.update(ln=True, eps=float(ln.eps))
+            if ln.elementwise_affine:
+                kw.update(gamma=ln.weight.detach().cpu().numpy(), beta=ln.bias.detach().cpu().numpy())
+        if not self.bn_relu:                                   # affine -> act -> norm
+            epilogue = act if act in HIP_ACTIVATIONS else None  # e.g. ReLU in front of a LayerNorm stays in the epilogue
+            y = self.affine.emit(inputs, act1=epilogue)
+            if epilogue is None:
+                kw.update(act0=act, slope0=slope)
+            if ln is None and self.batchnorm is not None:
+                kw["scale1"], kw["shift1"] = self.folded_batchnorm()
+        elif ln is None:                                       # affine -> BatchNorm (epilogue) -> act
+            scale, shift = self.folded_batchnorm()
+            y = self.affine.emit(inputs, scale=scale, shift=shift)
+            kw.update(act0=act, slope0=slope)
+        else:                                                  # affine -> LayerNorm -> act
+            y = self.affine.emit(inputs)
+            kw.update(act1=act, slope1=slope)
+        return _ir.Sym(y.graph, y.graph.rowop(y.view, **kw), y.rank)
 
 
 class ReluBatchNormTdnnLayer(_BaseActivationBatchNorm):

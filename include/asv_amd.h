@@ -85,6 +85,13 @@ int         asv_device_count(int *count);
 #define ASV_ACT_RELU    1
 #define ASV_ACT_TANH    2
 #define ASV_ACT_SIGMOID 3
+/* the row op's activations (asv_rowop_desc_t only: every other entry point rejects them) */
+#define ASV_ACT_LEAKY_RELU   4   /* x > 0 ? x : slope * x                                   */
+#define ASV_ACT_SELU         5   /* torch.nn.SELU                                           */
+#define ASV_ACT_MISH         6   /* x * tanh(softplus(x)), softplus(x) = x beyond 20        */
+#define ASV_ACT_SWISH        7   /* x * sigmoid(x) (torch.nn.SiLU)                          */
+#define ASV_ACT_GELU         8   /* 0.5 x (1 + erf(x / sqrt 2)), the exact form             */
+#define ASV_ACT_DOUBLE_SWISH 9   /* x * sigmoid(x - 1)                                      */
 
 #define ASV_DOMAIN_FRAMES 0  /* one row per frame, ragged over utterance segments */
 #define ASV_DOMAIN_UTTS   1  /* one row per utterance segment (after pooling); always f32 */
@@ -260,6 +267,37 @@ typedef struct asv_eltwise_desc {
 } asv_eltwise_desc_t;
 int asv_net_add_eltwise(asv_net_t *net, const asv_eltwise_desc_t *d);
 
+/* Row op: the activations the GEMM epilogues do not have and LayerNorm over the channels (libs/nnet/activation.py:69-94;
+ * _BaseActivationBatchNorm with ln_replace, components.py:365-386), as one pass over the rows.  For every valid row, with
+ * z = in[row, 0:channels]:
+ *   z = z * scale0 + shift0                      (optional)
+ *   z = act0(z)
+ *   if ln: mu = mean_c z;  var = mean_c (z - mu)^2 (biased, F.layer_norm);  z = (z - mu) / sqrt(var + eps) [* gamma + beta]
+ *   z = act1(z)
+ *   z = z * scale1 + shift1                      (optional)
+ * - the reference's four orders: act -> BN (act0, scale1), BN -> act (scale0, act0), act -> LN (act0, ln), LN -> act (ln, act1).
+ * The statistics run over the `channels` real channels of the view, never over the padded pitch.  act0 / act1: any ASV_ACT_*;
+ * slope0 / slope1: the negative slope of ASV_ACT_LEAKY_RELU.  Frames, sequence and utts domains (grids are refused); out may be
+ * the input view itself (in place), otherwise the two views must not overlap.  Rows that are not valid (gaps) and the columns
+ * that pad the view to a whole 16-byte piece are written as zeros, as asv_net_add_eltwise writes them.  The activations are
+ * evaluated in f32 with the accurate library functions; the LayerNorm sums and the normalisation - and act0 when ln follows it -
+ * in float64, rounded once.
+ * A layer next to a row op is never merged into a chain / fused-pooling kernel through it, and a buffer it reads holds plain rows.
+ * All host arrays ([channels] each) are copied during the call. */
+typedef struct asv_rowop_desc {
+  uint32_t struct_size;
+  int32_t channels;
+  int32_t in_buf, in_ch_off, out_buf, out_ch_off;
+  int32_t act0, act1;
+  float   slope0, slope1;
+  int32_t ln;
+  float   eps;                   /* > 0 with ln (the reference: 1e-5)                          */
+  const float *scale0, *shift0;  /* both or neither                                            */
+  const float *gamma, *beta;     /* LayerNorm's elementwise affine: both or neither, with ln   */
+  const float *scale1, *shift1;  /* both or neither                                            */
+} asv_rowop_desc_t;
+int asv_net_add_rowop(asv_net_t *net, const asv_rowop_desc_t *d);
+
 /* ResNetXvector's `x.unsqueeze(1)` (resnet_xvector.py:191): the input features [T][F] become a
  * one-channel grid buffer (domain: time_shift 0, width = feat_dim). */
 typedef struct asv_grid_input_desc {
@@ -340,6 +378,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream);
 #define ASV_KERNEL_CONV_WIDE 11   /* grid_conv_wide_kernel: C = 128 / 256 */
 #define ASV_KERNEL_CONV_S2D 12    /* grid_conv_s2d_kernel: the 128 -> 64 space-to-depth form of the stride-2 convolution */
 #define ASV_KERNEL_RES2N 13       /* kernels_res2n.hip: res2n_chain_kernel, the 64-wide Res2 chain as one launch */
+#define ASV_KERNEL_ROWOP 14       /* kernels_rowop.hip: rowop_kernel, the activation / LayerNorm row pass */
 unsigned long long asv_kernel_launch_count(int which);
 
 /* Bytes of device memory currently held by the net (weights + activation arena). */
@@ -369,6 +408,13 @@ int asv_tdnn_forward(const asv_tdnn_desc_t *d, int precision, unsigned flags,
  * y device [n_utts][channels*(1+stddev)] f32. */
 int asv_stats_pool_forward(const float *x, int channels, const int32_t *offsets, int n_utts,
                            int stddev, int unbiased, int var_mode, float eps, float *y, void *stream);
+/* One row op on rows of `width` channels.  x device [rows][width] f32, y device [rows][width] f32; the rows are stored in
+ * `precision`'s element type (utts domain: always f32) in buffer 1, the op's input (d->in_buf and the desc's buffer ids are
+ * ignored but for d->out_buf: 1 = in place, anything else = a second buffer that starts as a copy of the first); y receives the
+ * WHOLE output buffer, so columns outside the output view show what the op left of them.  domain ASV_DOMAIN_FRAMES: rows =
+ * offsets[n_utts], ragged segments; ASV_DOMAIN_UTTS: rows = n_utts, every utterance of `offsets` one frame long. */
+int asv_rowop_forward(const asv_rowop_desc_t *d, int precision, int domain, int width, const float *x, const int32_t *offsets,
+                      int n_utts, float *y, void *stream);
 
 /* ---- scoring back-end --------------------------------------------------------------- */
 /* In-place x <- (x - mean) if mean != NULL, then x <- x / ||x||_2 if normalize
