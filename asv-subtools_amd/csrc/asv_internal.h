@@ -356,6 +356,23 @@ struct RowopKernelParams {
 };
 int launch_rowop(const RowopKernelParams &p, int et, hipStream_t s);
 
+// the tap-table grid convolution (kernels_conv_taps.hip, asv_grid_conv_desc_t): stride 1, up to ASV_GRID_CONV_MAX_TAPS row offsets within the
+// halo of a reach-2 grid, bias and ReLU; rows of element type `et` in and out (f32 rows in every f32-storage precision mode)
+constexpr int kConvTapsTileRows = 128;       // output rows per workgroup
+constexpr int kConvTapsMaxHalo = 168;        // >= 2 * 83 + 2 (the widest reach-2 grid), a multiple of 8
+struct ConvTapsParams {
+  const void *x; void *y;                    // already offset to their channel views
+  const void *w;                             // fragments of pack_grid_conv_taps, element type of the rows
+  const float *bias;                         // [nf_total * 32]
+  const uint32_t *row_valid;
+  const void *zero16;                        // >= 16 bytes of device zeros
+  int ldx, ldy, rows, cin_pad, cout_store, nf_total, n_taps, halo_pad, relu;
+  int off[ASV_GRID_CONV_MAX_TAPS];           // row offsets dt * pitch + df, in table order
+};
+size_t grid_conv_taps_frag_bytes(int cin_pad, int nf_total, int n_taps, int et);
+void pack_grid_conv_taps(const float *w, int out_ch, int in_ch, int n_taps, int cin_pad, int nf_total, int et, void *dst);
+int launch_grid_conv_taps(const ConvTapsParams &p, int et, hipStream_t s);
+
 // float64 score matrices of the PLDA back-end (kernels_score_matrix.hip): C[i][j] = sum_k A[i][k] B[j][k] + row[i] + col[j] on the f64
 // matrix instruction.  A [m][kp], B [n][kp] float64 with kp a multiple of kScoreMatrixKChunk and zeros beyond the real K (the
 // preparation kernels write them), row [m], col [n] or nullptr, C dense [m][n] float (the LLR) or double (two-covariance).

@@ -152,11 +152,13 @@ struct Buffer {
 struct Domain {
   int kind;                // ASV_DOMAIN_FRAMES / ASV_DOMAIN_UTTS / 2 (grid)
   int shift = 0, width = 1, pitch = 1;
-  int halo() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : (kind == ASV_DOMAIN_UTTS ? 0 : pitch + 1); }
-  int gap() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : pitch + 2; }
+  int reach = 1;           // grids: 2 = pitch >= width + 2 and gaps that cover +-(2 pitch + 2) rows (asv_net_define_grid_reach)
+  int halo() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : (kind == ASV_DOMAIN_UTTS ? 0 : pitch + 1); }      // what a TDNN layer may reach
+  int conv_halo() const { return kind == 2 ? reach * pitch + reach : 0; }                                          // what asv_net_add_grid_conv may reach
+  int gap() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : (reach == 2 ? 2 * pitch + 3 : pitch + 2); }
 };
 
-enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10, OP_ROWOP = 11 };
+enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10, OP_ROWOP = 11, OP_GRID_CONV = 12 };
 
 struct Op {
   OpKind kind;
@@ -173,6 +175,7 @@ struct Op {
   asv_res2n_desc_t res2n;        // likewise (bias stays nullptr when the op has none)
   asv_res2_desc_t res2;          // fragments in `wfrag`, per-branch constants in bias / scale / shift
   asv_rowop_desc_t rop;          // host pointers nulled; the per-channel tables live in `rop_tab`
+  asv_grid_conv_desc_t gconv;    // host pointers nulled; fragments of pack_grid_conv_taps in `wconv`, bias in `bias`
   // device parameters
   void *w = nullptr;
   void *wfrag = nullptr;         // fragment-ordered copy for the variant-3 kernel (bf16 frame layers); pooled layers: bf16 hi halves
@@ -205,8 +208,8 @@ struct DevMem {
   size_t cap = 0;
 };
 
-const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain", "rowop"};
-enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_ROWOP, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
+const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain", "rowop", "grid_conv_taps"};
+enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_ROWOP, K_CONV_TAPS, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
 
 }  // namespace
 }  // namespace asv
@@ -263,7 +266,7 @@ struct asv_net {
 
 namespace {
 
-std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_ROWOP + 1];       // asv_kernel_launch_count (ids start at 1)
+std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_CONV_TAPS + 1];       // asv_kernel_launch_count (ids start at 1)
 
 // the range-status word of the f32x kernels lives behind the zero page's zeros (own 64-byte line; kernels only ever OR into it)
 uint32_t *status_word(asv_net *net) { return reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(net->zero_page) + 128); }
@@ -487,6 +490,19 @@ int asv_net_define_grid(asv_net_t *net, int time_shift, int width, int pitch) {
   ASV_REQUIRE(width >= 1 && (pitch >= width + 1 || (width == 1 && pitch == 1)) && pitch + 1 <= 84, "asv_net_define_grid: need 1 <= width < pitch <= 83, or width = pitch = 1 (got %d, %d)", width, pitch);
   Domain d{2};
   d.shift = time_shift; d.width = width; d.pitch = pitch;
+  net->domains.push_back(d);
+  return (int)net->domains.size() - 1;
+}
+
+int asv_net_define_grid_reach(asv_net_t *net, int time_shift, int width, int pitch, int reach) {
+  ASV_REQUIRE(reach == 1 || reach == 2, "asv_net_define_grid_reach: reach %d (1 or 2)", reach);
+  if (reach == 1) return asv_net_define_grid(net, time_shift, width, pitch);
+  ASV_REQUIRE(net && !net->finalized, "asv_net_define_grid_reach: net is null or finalized");
+  ASV_REQUIRE(time_shift >= 0 && time_shift <= 8, "asv_net_define_grid_reach: time_shift %d", time_shift);
+  ASV_REQUIRE(width >= 1 && pitch >= width + 2 && 2 * pitch + 2 <= kConvTapsMaxHalo && pitch + 1 <= 84,
+              "asv_net_define_grid_reach: reach 2 needs 1 <= width, width + 2 <= pitch <= 83 (got %d, %d)", width, pitch);
+  Domain d{2};
+  d.shift = time_shift; d.width = width; d.pitch = pitch; d.reach = 2;
   net->domains.push_back(d);
   return (int)net->domains.size() - 1;
 }
@@ -891,6 +907,42 @@ int asv_net_add_rowop(asv_net_t *net, const asv_rowop_desc_t *d) {
   return ASV_OK;
 }
 
+int asv_net_add_grid_conv(asv_net_t *net, const asv_grid_conv_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_grid_conv: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_grid_conv_desc_t), "asv_net_add_grid_conv: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(asv_grid_conv_desc_t));
+  int rc;
+  if ((rc = check_view(net, d->in_buf, d->in_ch_off, d->in_ch, "grid_conv input"))) return rc;
+  if ((rc = check_view(net, d->out_buf, d->out_ch_off, d->out_ch, "grid_conv output"))) return rc;
+  const int dom = net->bufs[d->in_buf].domain;
+  const Domain &dm = net->domains[dom];
+  ASV_REQUIRE(dm.kind == 2 && !net->is_sequence(dom), "grid_conv: the input must live on a (time, frequency) grid");
+  ASV_REQUIRE(net->bufs[d->out_buf].domain == dom && d->out_buf != 0, "grid_conv: bad output buffer (the input's grid, never the feature buffer)");
+  const int cin_pad = round_up(d->in_ch, kChanAlign), cout_store = round_up(d->out_ch, kChanAlign), nf_total = (d->out_ch + 31) / 32;
+  ASV_REQUIRE(d->in_ch_off + cin_pad <= net->bufs[d->in_buf].ld && d->out_ch_off + cout_store <= net->bufs[d->out_buf].ld, "grid_conv: padded view exceeds the buffer pitch");
+  // tiles of other workgroups read the halo rows of the input while this one stores its output rows
+  ASV_REQUIRE(d->in_buf != d->out_buf || d->in_ch_off + cin_pad <= d->out_ch_off || d->out_ch_off + cout_store <= d->in_ch_off,
+              "grid_conv: the output slice overlaps the input slice of the same buffer");
+  ASV_REQUIRE(d->n_taps >= 1 && d->n_taps <= ASV_GRID_CONV_MAX_TAPS, "grid_conv: n_taps %d (1 .. %d)", d->n_taps, ASV_GRID_CONV_MAX_TAPS);
+  for (int t = 0; t < d->n_taps; ++t) {
+    ASV_REQUIRE(std::abs(d->dt[t]) <= dm.reach && std::abs(d->df[t]) <= dm.reach, "grid_conv: tap (%d, %d) beyond the reach %d of this grid (asv_net_define_grid_reach)",
+                d->dt[t], d->df[t], dm.reach);
+    for (int u = 0; u < t; ++u) ASV_REQUIRE(d->dt[u] != d->dt[t] || d->df[u] != d->df[t], "grid_conv: tap (%d, %d) appears twice", d->dt[t], d->df[t]);
+  }
+  ASV_REQUIRE(d->weight != nullptr, "grid_conv: null weight");
+  ASV_REQUIRE(d->act == ASV_ACT_NONE || d->act == ASV_ACT_RELU, "grid_conv: activation %d (none or ReLU)", d->act);
+  Op op; op.kind = OP_GRID_CONV; op.gconv = *d;
+  op.cin_pad = cin_pad; op.cout_store = cout_store; op.cout_pad = nf_total * 32;
+  ASV_ON_DEVICE(net->device);
+  const int et = net->dom_et(dom);
+  std::vector<unsigned char> frags(grid_conv_taps_frag_bytes(cin_pad, nf_total, d->n_taps, et));
+  pack_grid_conv_taps(d->weight, d->out_ch, d->in_ch, d->n_taps, cin_pad, nf_total, et, frags.data());
+  if ((rc = dev_upload(net, frags.data(), frags.size(), &op.wconv))) return rc;
+  if ((rc = upload_padded(net, d->bias, d->bias ? d->out_ch : 0, op.cout_pad, 0.0f, &op.bias))) return rc;
+  op.gconv.weight = nullptr; op.gconv.bias = nullptr;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
 int asv_net_add_grid_input(asv_net_t *net, const asv_grid_input_desc_t *d) {
   ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_grid_input: net is null or finalized");
   ASV_REQUIRE(d->struct_size == sizeof(asv_grid_input_desc_t), "asv_net_add_grid_input: struct_size mismatch");
@@ -976,7 +1028,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                              o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.x_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.logit_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
-                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1};
+                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1, o.kind == OP_GRID_CONV ? o.gconv.in_buf : -1};
         for (int rbuf : reads) other_reader |= (rbuf == d.out_buf);
       }
       if (other_reader || d.out_buf == out_buf) continue;
@@ -995,7 +1047,7 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                            o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                            o.kind == OP_ELTWISE ? o.elt.seg_scale_buf : -1, o.kind == OP_ELTWISE ? o.elt.seg_norm_buf : -1, o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
                            o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_IM2COL ? o.i2c.seg_scale_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_GRID_INPUT ? o.gin.in_buf : -1,
-                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1};
+                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1, o.kind == OP_GRID_CONV ? o.gconv.in_buf : -1};
       for (int rbuf : reads) if (rbuf == buf) return false;
     }
     return true;
@@ -1131,7 +1183,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream) {
 }
 
 unsigned long long asv_kernel_launch_count(int which) {
-  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_ROWOP) ? g_kernel_launches[which].load() : 0ull;
+  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_CONV_TAPS) ? g_kernel_launches[which].load() : 0ull;
 }
 
 size_t asv_net_device_bytes(const asv_net_t *net) {
@@ -1151,7 +1203,8 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
   for (size_t i = 0; i < net->bufs.size(); ++i) {
     const Domain &dm = net->domains[net->bufs[i].domain];
     char dname[64];
-    if (dm.kind == 2) snprintf(dname, sizeof(dname), "grid(T/%d x %d, pitch %d)", 1 << dm.shift, dm.width, dm.pitch);
+    if (dm.kind == 2 && dm.reach == 2) snprintf(dname, sizeof(dname), "grid(T/%d x %d, pitch %d, reach 2)", 1 << dm.shift, dm.width, dm.pitch);
+    else if (dm.kind == 2) snprintf(dname, sizeof(dname), "grid(T/%d x %d, pitch %d)", 1 << dm.shift, dm.width, dm.pitch);
     else snprintf(dname, sizeof(dname), "%s", dm.kind == ASV_DOMAIN_FRAMES ? "frames" : "utts");
     snprintf(line, sizeof(line), "  buf %zu: %s channels=%d ld=%d\n", i, dname, net->bufs[i].channels, net->bufs[i].ld);
     s += line;
@@ -1209,6 +1262,10 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
         snprintf(line, sizeof(line), "  op %zu: rowop %d[%d:+%d] -> %d[%d] affine0=%d act0=%d ln=%d(affine=%d eps=%g) act1=%d affine1=%d\n", i, op.rop.in_buf, op.rop.in_ch_off,
                  op.rop.channels, op.rop.out_buf, op.rop.out_ch_off, op.rop_tab[0] != nullptr, op.rop.act0, op.rop.ln, op.rop_tab[2] != nullptr, (double)op.rop.eps,
                  op.rop.act1, op.rop_tab[4] != nullptr);
+        break;
+      case OP_GRID_CONV:
+        snprintf(line, sizeof(line), "  op %zu: grid_conv %d[%d:+%d] -> %d[%d:+%d] taps=%d act=%d bias=%d\n", i, op.gconv.in_buf, op.gconv.in_ch_off, op.gconv.in_ch,
+                 op.gconv.out_buf, op.gconv.out_ch_off, op.gconv.out_ch, op.gconv.n_taps, op.gconv.act, op.bias != nullptr);
         break;
     }
     s += line;
@@ -1882,6 +1939,31 @@ int run_ops(RunCtx &c, size_t n_ops) {
         if ((rc = prof.begin(K_ROWOP, 0, (int)i))) return rc;
         if ((rc = launch_rowop(p, net->dom_et(domid), c.s))) return rc;
         ++g_kernel_launches[ASV_KERNEL_ROWOP];
+        if ((rc = prof.end())) return rc;
+        break;
+      }
+      case OP_GRID_CONV: {
+        const auto &d = op.gconv;
+        const int domid = net->bufs[d.in_buf].domain;
+        const Domain &dm = net->domains[domid];
+        const DomainRun &dr = c.dom[domid];
+        ASV_REQUIRE(!c.buf_image[d.in_buf], "grid_conv: image rows reached the grid convolution (internal)");
+        ConvTapsParams p;
+        memset(&p, 0, sizeof(p));
+        p.x = view(c, d.in_buf, d.in_ch_off); p.ldx = net->bufs[d.in_buf].ld;
+        p.y = view(c, d.out_buf, d.out_ch_off); p.ldy = net->bufs[d.out_buf].ld;
+        p.w = op.wconv; p.bias = op.bias; p.row_valid = dr.row_valid; p.zero16 = net->zero_page;
+        p.rows = dr.rows_pad; p.cin_pad = op.cin_pad; p.cout_store = op.cout_store; p.nf_total = op.cout_pad / 32;
+        p.n_taps = d.n_taps; p.relu = d.act == ASV_ACT_RELU;
+        int halo = 0;
+        for (int t = 0; t < d.n_taps; ++t) { p.off[t] = d.dt[t] * dm.pitch + d.df[t]; halo = std::max(halo, std::abs(p.off[t])); }
+        ASV_REQUIRE(halo <= dm.conv_halo() && halo <= dm.gap(), "grid_conv: tap offset %d beyond the grid's %d zero rows (internal)", halo, dm.conv_halo());
+        p.halo_pad = round_up(halo, 8);
+        double frames = 0;                            // valid positions of the batch on this grid
+        for (int32_t len : bp.dom[domid].seg_len) frames += (double)len / dm.pitch * dm.width;
+        if ((rc = prof.begin(K_CONV_TAPS, 2.0 * frames * d.in_ch * d.out_ch * d.n_taps, (int)i))) return rc;
+        if ((rc = launch_grid_conv_taps(p, net->dom_et(domid), c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_CONV_TAPS];
         if ((rc = prof.end())) return rc;
         break;
       }

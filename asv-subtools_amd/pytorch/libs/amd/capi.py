@@ -26,6 +26,8 @@ KERNEL_MQ_ATTPOOL = 7
 KERNEL_CONV_C1, KERNEL_CONV_NARROW, KERNEL_CONV_NARROW_PERS, KERNEL_CONV_WIDE, KERNEL_CONV_S2D = 8, 9, 10, 11, 12
 KERNEL_RES2N = 13
 KERNEL_ROWOP = 14
+KERNEL_CONV_TAPS = 15
+GRID_CONV_MAX_TAPS = 25
 RES2N_TILE_ROWS = 192          # ASV_RES2N_TILE_ROWS: rows a workgroup of res2n_chain_kernel produces
 
 ACT_BY_NAME = {None: ACT_NONE, "": ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "tanh": ACT_TANH,
@@ -168,6 +170,17 @@ class Im2colDesc(C.Structure):
     ]
 
 
+class GridConvDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("in_buf", C.c_int32), ("in_ch_off", C.c_int32), ("in_ch", C.c_int32),
+        ("out_buf", C.c_int32), ("out_ch_off", C.c_int32), ("out_ch", C.c_int32),
+        ("n_taps", C.c_int32), ("dt", C.c_int32 * GRID_CONV_MAX_TAPS), ("df", C.c_int32 * GRID_CONV_MAX_TAPS),
+        ("weight", c_float_p), ("bias", c_float_p),
+        ("act", C.c_int32),
+    ]
+
+
 class FbankOpts(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -209,6 +222,7 @@ SYMBOLS = [
     "asv_plda_train", "asv_scatter_f64", "asv_class_scatter_f64",
     "asv_fbank_num_frames", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
     "asv_ingest_frames", "asv_decode_compressed", "asv_ingest_windows", "asv_desilence_pcm16",
+    "asv_net_define_grid_reach", "asv_net_add_grid_conv",
 ]
 
 
@@ -242,6 +256,8 @@ def lib():
     L.asv_net_destroy.argtypes = [vp]; L.asv_net_destroy.restype = None
     L.asv_net_new_buffer.argtypes = [vp, ci, ci]
     L.asv_net_define_grid.argtypes = [vp, ci, ci, ci]
+    L.asv_net_define_grid_reach.argtypes = [vp, ci, ci, ci, ci]
+    L.asv_net_add_grid_conv.argtypes = [vp, C.POINTER(GridConvDesc)]
     L.asv_net_add_grid_input.argtypes = [vp, C.POINTER(GridInputDesc)]
     L.asv_net_add_im2col.argtypes = [vp, C.POINTER(Im2colDesc)]
     L.asv_net_add_grid_flatten.argtypes = [vp, C.POINTER(GridFlattenDesc)]

@@ -114,11 +114,6 @@ class Engine(object):
         L, g = self.lib, self.graph
         buf_of = {0: 0}
         dom_of = {0: capi.DOMAIN_FRAMES, 1: capi.DOMAIN_UTTS}
-        for i, spec in enumerate(g.domains):
-            if spec[0] == "grid":
-                dom_of[i] = capi.check(L.asv_net_define_grid(self._net, spec[1], spec[2], spec[3]), "asv_net_define_grid")
-            elif spec[0] == "seq":                   # one row per frame at the grid's rate = a grid of width 1, pitch 1
-                dom_of[i] = capi.check(L.asv_net_define_grid(self._net, spec[1], 1, 1), "asv_net_define_grid")
         # one device buffer per IR tensor that something writes as a whole or in slices
         # 16-bit engines run every Res2NetBlock as one kernel (kernels_res2.hip); the parity modes keep one layer per branch
         fuse = self.precision_base in H16_MODES and (self.flags & (capi.FLAG_REF_KERNELS | capi.FLAG_NO_FUSE | capi.FLAG_SMALL_TILES)) == 0
@@ -133,6 +128,16 @@ class Engine(object):
                 ops = g.fused_mqpool_ops(ops)        # likewise: the (head, query) poolings of MQMHASP as one launch
         self.ops = ops                               # the program as uploaded (op indices of the profiling rows refer to it)
         written = sorted({op.out.tid for op in ops} | {op.out2.tid for op in ops if getattr(op, "out2", None) is not None})
+        live_domains = {g.tensors[tid][0] for tid in written}      # a domain whose tensors were all optimised away (the reach-1 grid `x.unsqueeze(1)`
+        for i, spec in enumerate(g.domains):                       # makes in front of a RepSPK trunk) gets no row maps
+            if i not in live_domains:
+                continue
+            if spec[0] == "grid" and len(spec) > 4:      # a reach-2 grid (ir.Graph.grid_domain)
+                dom_of[i] = capi.check(L.asv_net_define_grid_reach(self._net, spec[1], spec[2], spec[3], spec[4]), "asv_net_define_grid_reach")
+            elif spec[0] == "grid":
+                dom_of[i] = capi.check(L.asv_net_define_grid(self._net, spec[1], spec[2], spec[3]), "asv_net_define_grid")
+            elif spec[0] == "seq":                   # one row per frame at the grid's rate = a grid of width 1, pitch 1
+                dom_of[i] = capi.check(L.asv_net_define_grid(self._net, spec[1], 1, 1), "asv_net_define_grid")
         for tid in written:
             dom, ch = g.tensors[tid]
             buf_of[tid] = capi.check(L.asv_net_new_buffer(self._net, dom_of[dom], ch), "asv_net_new_buffer")
@@ -254,6 +259,20 @@ class Engine(object):
                 d.in_buf, d.in_ch_off = bv(op.inp)
                 d.out_buf, d.out_ch_off = bv(op.out)
                 capi.check(L.asv_net_add_rowop(self._net, C.byref(d)), "asv_net_add_rowop")
+                del keep
+            elif op.kind == "grid_conv":
+                d = capi.GridConvDesc()
+                d.struct_size = C.sizeof(capi.GridConvDesc)
+                d.in_buf, d.in_ch_off = bv(op.inp)
+                d.out_buf, d.out_ch_off = bv(op.out)
+                d.in_ch, d.out_ch, d.n_taps = op.inp.channels, op.out.channels, len(op.taps)
+                for i, (dt, df) in enumerate(op.taps):
+                    d.dt[i], d.df[i] = dt, df
+                keep = [op.weight, op.bias]
+                d.weight = capi.f32_ptr(op.weight)
+                d.bias = capi.f32_ptr(op.bias) if op.bias is not None else None
+                d.act = capi.ACT_BY_NAME[op.act]
+                capi.check(L.asv_net_add_grid_conv(self._net, C.byref(d)), "asv_net_add_grid_conv")
                 del keep
             elif op.kind == "grid_input":
                 d = capi.GridInputDesc()

@@ -48,7 +48,7 @@ class View(object):
 
 
 class Op(object):
-    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','rowop','cat','grid_input','im2col'}; `out` is a View covering
+    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','rowop','cat','grid_input','im2col','grid_conv'}; `out` is a View covering
     a whole tensor until concat elision redirects it into a slice of a wider one."""
 
     def __init__(self, kind, out, **attrs):
@@ -68,7 +68,7 @@ class Op(object):
             names = ("a", "b", "c", "seg_scale", "seg_norm", "d")
         elif self.kind == "im2col":
             names = ("inp", "b", "seg_scale")
-        elif self.kind in ("grid_input", "res2", "res2n", "flatten", "rowop"):
+        elif self.kind in ("grid_input", "res2", "res2n", "flatten", "rowop", "grid_conv"):
             names = ("inp",)
         else:
             return list(self.parts)
@@ -77,7 +77,7 @@ class Op(object):
     def input_names(self):
         return {"tdnn": ("inp", "inp2", "seg_bias", "seg_scale", "res"), "pool": ("inp",),
                 "attpool": ("x", "logits"), "mqattpool": ("x", "logits"), "lde": ("x",), "eltwise": ("a", "b", "c", "seg_scale", "seg_norm", "d"), "cat": (), "grid_input": ("inp",),
-                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",), "rowop": ("inp",)}[self.kind]
+                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",), "rowop": ("inp",), "grid_conv": ("inp",)}[self.kind]
 
 
 class Graph(object):
@@ -85,7 +85,8 @@ class Graph(object):
         self.tensors = []          # [(domain, channels)]
         self.ops = []
         self.feat_dim = int(feat_dim)
-        # row domains: 0 frames, 1 utts, >= 2 (time, frequency) grids ("grid", time_shift, width, pitch) and the sequences
+        # row domains: 0 frames, 1 utts, >= 2 (time, frequency) grids ("grid", time_shift, width, pitch) - reach-2 grids
+        # ("grid", time_shift, width, pitch, 2): pitch >= width + 2 and wider gaps, for the 5 x 5 kernels of RepSPK - and the sequences
         # ("seq", time_shift) their flattened [B, C*F, T'] views live on (one row per frame of the subsampled time axis)
         self.domains = [("frames",), ("utts",)]
         self.new_tensor(DOMAIN_FRAMES, feat_dim)        # tensor 0 = input features
@@ -101,10 +102,16 @@ class Graph(object):
     def full_view(self, tid):
         return View(tid, 0, self.tensors[tid][1])
 
-    def grid_domain(self, shift, width, pitch=None):
-        spec = ("grid", int(shift), int(width), int(pitch if pitch is not None else width + 1))
+    def grid_domain(self, shift, width, pitch=None, reach=1):
+        spec = ("grid", int(shift), int(width), int(pitch if pitch is not None else width + reach))
+        if reach == 2:
+            if spec[3] < width + 2:
+                raise TraceError("a reach-2 grid needs pitch >= width + 2 (got width %d, pitch %d)" % (width, spec[3]))
+            spec = spec + (2,)
+        elif reach != 1:
+            raise TraceError("grid reach %r (1 or 2)" % (reach,))
         if spec[3] + 1 > 84:
-            raise TraceError("2-D trunk: %d frequency bins exceed the widest window the MI355X conv kernel stages (82)" % width)
+            raise TraceError("2-D trunk: %d frequency bins exceed the widest window the MI355X conv kernel stages (%d)" % (width, 83 - reach))
         if spec not in self.domains:
             self.domains.append(spec)
         return self.domains.index(spec)
@@ -125,6 +132,10 @@ class Graph(object):
     def grid_spec(self, tid):
         d = self.domains[self.domain(tid)]
         return d if d[0] == "grid" else None
+
+    def grid_reach(self, tid):
+        d = self.grid_spec(tid)
+        return (d[4] if len(d) > 4 else 1) if d is not None else 0
 
     # ---- op constructors -------------------------------------------------------------
     def tdnn(self, inp, weight, bias, taps, w_left, act1=None, scale=None, shift=None, affine_first=False,
@@ -154,10 +165,10 @@ class Graph(object):
                            per_bin=bool(per_bin)))
         return out
 
-    def grid_input(self, inp=None):
+    def grid_input(self, inp=None, reach=1):
         """features [T][F] (raw input or a normalised copy) -> one-channel (time, frequency) grid."""
         inp = inp or self.full_view(0)
-        dom = self.grid_domain(0, self.feat_dim)
+        dom = self.grid_domain(0, self.feat_dim, reach=reach)
         out = self.full_view(self.new_tensor(dom, 1))
         self.ops.append(Op("grid_input", out, inp=inp))
         return out
@@ -168,9 +179,28 @@ class Graph(object):
         assert g is not None and inp.ch_off == 0 and inp.channels == self.tensors[inp.tid][1]
         if inp.channels % CHAN_ALIGN != 0:
             raise TraceError("strided 2-D convolution over %d channels: the gather needs a multiple of %d" % (inp.channels, CHAN_ALIGN))
-        dom = self.grid_domain(g[1] + (1 if stride == 2 else 0), (g[2] + stride - 1) // stride)
+        dom = self.grid_domain(g[1] + (1 if stride == 2 else 0), (g[2] + stride - 1) // stride, reach=self.grid_reach(inp.tid))
         out = self.full_view(self.new_tensor(dom, inp.channels * len(taps)))
         self.ops.append(Op("im2col", out, inp=inp, taps=[(int(a), int(b)) for a, b in taps], stride=int(stride)))
+        return out
+
+    def grid_conv(self, inp, weight, bias, taps, act=None):
+        """Stride-1 convolution with a tap table of its own (asv_grid_conv_desc_t, kernels_conv_taps.hip): taps [(dt, df)] within the
+        grid's reach, weight [out, in, len(taps)], bias [out] or None, act None | 'relu'."""
+        g = self.grid_spec(inp.tid)
+        if g is None:
+            raise TraceError("grid_conv applied to a tensor that is not on a (time, frequency) grid")
+        weight = np.ascontiguousarray(weight, dtype=np.float32)
+        taps = [(int(a), int(b)) for a, b in taps]
+        assert weight.ndim == 3 and weight.shape[1] == inp.channels and weight.shape[2] == len(taps), (weight.shape, inp, len(taps))
+        reach = self.grid_reach(inp.tid)
+        if not 1 <= len(taps) <= 25 or len(set(taps)) != len(taps) or max(max(abs(a), abs(b)) for a, b in taps) > reach:
+            raise TraceError("grid_conv: %d taps %s on a reach-%d grid (1 .. 25 distinct offsets within the reach)" % (len(taps), taps, reach))
+        if act not in (None, "relu"):
+            raise TraceError("grid_conv: activation %r (none or relu)" % (act,))
+        out = self.full_view(self.new_tensor(self.domain(inp.tid), weight.shape[0]))
+        self.ops.append(Op("grid_conv", out, inp=inp, weight=weight, bias=None if bias is None else np.ascontiguousarray(bias, dtype=np.float32),
+                           taps=taps, act=act))
         return out
 
     def flatten_grid(self, inp):
@@ -638,6 +668,8 @@ class Graph(object):
                 ins, extra = repr(op.inp), "taps=%d stride=%d" % (len(op.taps), op.stride)
             elif op.kind == "flatten":
                 ins, extra = repr(op.inp), ""
+            elif op.kind == "grid_conv":
+                ins, extra = repr(op.inp), "taps=%d act=%s" % (len(op.taps), op.act)
             elif op.kind == "attpool":
                 ins, extra = "x=%r logits=%r" % (op.x, op.logits), "eps=%g" % op.eps
             elif op.kind == "mqattpool":
@@ -661,7 +693,7 @@ class Graph(object):
         (active taps only)."""
         per_frame = per_utt = 0
         for op in self.ops:
-            if op.kind != "tdnn":
+            if op.kind not in ("tdnn", "grid_conv"):
                 continue
             f = 2 * op.inp.channels * op.weight.shape[0] * len(op.taps) * (getattr(op, "alg_fraction", None) or 1.0)
             g = self.grid_spec(op.inp.tid)

@@ -83,6 +83,15 @@ def emit_conv_bn(x, conv, bn, relu):
     else:
         scale, shift = np.ones(conv.out_channels, dtype=np.float32), np.zeros(conv.out_channels, dtype=np.float32)
     w = _np(conv.weight).astype(np.float64) * scale.astype(np.float64)[:, None, None, None]       # [Cout, Cin, kF, kT]
+    return emit_conv_folded(x, w, shift, stride, relu)
+
+
+def emit_conv_folded(x, w, shift, stride, relu):
+    """The convolution w [Cout, Cin, k, k] (float64; k = 3 with pad 1, or 1; BatchNorm scales already in it) + per-channel `shift`
+    [-> ReLU], stride 1 | 2, on a rank-4 grid Sym: what emit_conv_bn lowers, and the folded 3 x 3 blocks of libs/nnet/repvgg.py."""
+    g = x.graph
+    spec = g.grid_spec(x.view.tid)
+    k = w.shape[2]
     cout, cin = w.shape[0], w.shape[1]
     half = k // 2
     pos = [(dt, df) for df in range(-half, half + 1) for dt in range(-half, half + 1)]             # (time, frequency) offsets

@@ -333,6 +333,33 @@ typedef struct asv_grid_flatten_desc {
 } asv_grid_flatten_desc_t;
 int asv_net_add_grid_flatten(asv_net_t *net, const asv_grid_flatten_desc_t *d);
 
+/* Grids whose layers reach TWO positions in time and frequency (the folded 5 x 5 kernels of the RepSPK blocks, libs/nnet/repvgg.py).
+ * asv_net_define_grid() means reach 1: one zero row behind the bins of a frame (pitch >= width + 1), pitch + 2 gap rows between
+ * utterances, taps within +-(pitch + 1) rows.  reach 2 needs pitch >= width + 2 (a frequency offset of +-2 lands in a zero row),
+ * puts 2 pitch + 3 gap rows between utterances (a time offset of +-2 lands in a gap) and lets asv_net_add_grid_conv reach
+ * +-(2 pitch + 2) rows; pitch <= 83.  Every other grid op (grid input, 9-tap layers within +-(pitch + 1), im2col, eltwise, pooling,
+ * flatten) runs on such a grid as on any other: they are driven by the row maps.  Returns the domain id. */
+int asv_net_define_grid_reach(asv_net_t *net, int time_shift, int width, int pitch, int reach);
+
+/* Stride-1 convolution on a grid with a tap table of its own (kernels_conv_taps.hip): out[(t, f)][co] =
+ * act(bias[co] + sum_k sum_ci weight[co][ci][k] * in[(t + dt[k], f + df[k])][ci]), zero outside the utterance, zeros on the rows
+ * that are not valid.  |dt[k]|, |df[k]| <= the reach of the grid both views live on; taps are distinct.  The kernel accumulates
+ * chunk of input channels outermost (32 f32 / 64 16-bit channels), then the taps in table order.  16-bit precision modes: 16-bit rows
+ * and weights, f32 accumulation; ASV_PREC_F32 and ASV_PREC_F32X (every option): f32 rows and weights on the f32-input matrix
+ * instruction.  The host arrays are copied during the call. */
+#define ASV_GRID_CONV_MAX_TAPS 25
+typedef struct asv_grid_conv_desc {
+  uint32_t struct_size;
+  int32_t in_buf, in_ch_off, in_ch;
+  int32_t out_buf, out_ch_off, out_ch;          /* disjoint from the input view                                     */
+  int32_t n_taps;                               /* 1 .. ASV_GRID_CONV_MAX_TAPS                                      */
+  int32_t dt[ASV_GRID_CONV_MAX_TAPS], df[ASV_GRID_CONV_MAX_TAPS];
+  const float *weight;                          /* dense [out_ch][in_ch][n_taps]                                    */
+  const float *bias;                            /* [out_ch] or NULL                                                 */
+  int32_t act;                                  /* ASV_ACT_NONE | ASV_ACT_RELU                                      */
+} asv_grid_conv_desc_t;
+int asv_net_add_grid_conv(asv_net_t *net, const asv_grid_conv_desc_t *d);
+
 /* Freezes the program; `out_buf` must be an utts-domain buffer: its first `embed_dim`
  * channels are the embedding. */
 int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim);
@@ -379,6 +406,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream);
 #define ASV_KERNEL_CONV_S2D 12    /* grid_conv_s2d_kernel: the 128 -> 64 space-to-depth form of the stride-2 convolution */
 #define ASV_KERNEL_RES2N 13       /* kernels_res2n.hip: res2n_chain_kernel, the 64-wide Res2 chain as one launch */
 #define ASV_KERNEL_ROWOP 14       /* kernels_rowop.hip: rowop_kernel, the activation / LayerNorm row pass */
+#define ASV_KERNEL_CONV_TAPS 15   /* kernels_conv_taps.hip: grid_conv_taps_kernel, the tap-table grid convolution (asv_net_add_grid_conv) */
 unsigned long long asv_kernel_launch_count(int which);
 
 /* Bytes of device memory currently held by the net (weights + activation arena). */
