@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/asv_amd.h"
+#include "host_convert.h"
 
 namespace asv {
 
@@ -62,7 +63,6 @@ struct DeviceGuard {
 #define ASV_ON_DEVICE(dev) ::asv::DeviceGuard _asv_dev_guard; do { int _rc = _asv_dev_guard.enter(dev); if (_rc) return _rc; } while (0)
 #define ASV_ON_OWNER(ptr, what) ::asv::DeviceGuard _asv_dev_guard; do { int _rc = _asv_dev_guard.enter_owner(ptr, what); if (_rc) return _rc; } while (0)
 
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // ---------------------------------------------------------------------------------------
@@ -149,17 +149,12 @@ struct PoolKernelParams {
 };
 constexpr int kPoolChunkRows = 2048;     // a property of the kernel, never of the batch: an utterance's mean does not depend on its neighbours
 
-// Element type of frames-domain storage and of the matrix operands: the launchers' `et` argument (a former `bool bf16`
-// converts to the first two values).
-enum : int { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };
-
 // launchers (kernels_*.hip).  et: element type of the activations (ET_*).
 int launch_tdnn_mfma(const TdnnKernelParams &p, int et, bool out_f32, hipStream_t s);
 int launch_tdnn_ref(const TdnnKernelParams &p, int et, bool out_f32, hipStream_t s);
 int launch_utts_gemm(const TdnnKernelParams &p, int rows_valid, bool split, hipStream_t s);
 // kernels_conv2d.hip: 3x3 grid convolutions with 32 / 64 channels (weights in p.wfrag, [tap][k-group][n-frag][lane][8])
 bool grid_conv_narrow_supported(const TdnnKernelParams &p, int et);
-size_t grid_conv_frag_elems(int cin_pad, int cout_pad32, int n_taps = 9);
 bool grid_conv_s2d_supported(const TdnnKernelParams &p, int et);      // 128 (4 phases x 32) -> 64 channels, 4 backward taps
 int launch_grid_conv_s2d(const TdnnKernelParams &p, hipStream_t s);
 int launch_grid_conv_narrow(const TdnnKernelParams &p, hipStream_t s, bool *persistent = nullptr);      // *persistent: which of its two kernels ran
@@ -170,9 +165,6 @@ int launch_grid_conv_c1(const TdnnKernelParams &p, hipStream_t s);
 // kernels_conv2d_x3.hip: the grid-domain layers of the f32x precision mode (f32 rows, three 16-bit matrix instructions per product);
 // weights in p.wconv as [chunk32][tap][k-group][n-fragment][hi | lo][lane][8], scaled by 1 / p.w_unscale
 bool grid_conv_x3_shape_ok(int cin_pad, int cout_store);
-size_t grid_conv_x3_frag_elems(int cin_pad, int cout_store, int n_taps);
-void pack_grid_conv_x3_frags(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps, int cin_pad, int cout_store,
-                             int et, float scale, uint16_t *dst);
 bool grid_conv_x3_supported(const TdnnKernelParams &p);
 int launch_grid_conv_x3(const TdnnKernelParams &p, hipStream_t s);
 int launch_splitk_epilogue(const TdnnKernelParams &p, int et, bool out_f32, hipStream_t s);
@@ -189,8 +181,6 @@ int launch_tdnn_p8_variant(const TdnnKernelParams &p, int variant, hipStream_t s
 // the same structure for the f32x mode: f32 rows split in registers, three matrix instructions per product (kernels_tdnn_p8x.hip); weights in p.wx3p
 bool tdnn_p8x_supported(const TdnnKernelParams &p);
 int launch_tdnn_p8x(const TdnnKernelParams &p, hipStream_t s);
-void pack_tdnn_weight_x3p(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps, int cout_pad, int cin_pad,
-                          int et, float scale, uint16_t *dst);
 // tdnn -> [1-tap 512 -> 512]* -> 1-tap + fused statistics pooling in one kernel, the 128 x 512 intermediate tiles resident in
 // LDS (kernels_tdnn_chain.hip).  Weight fragments as for the variant-3 kernel.
 constexpr int kChainWidth = 512;
@@ -265,8 +255,6 @@ struct Res2nKernelParams {
   int et;                                            // ET_BF16 / ET_F16
 };
 int launch_res2n_chain(const Res2nKernelParams &p, hipStream_t s);
-void pack_tdnn_weight_frags(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps,
-                            int cout_pad, int cin_pad, uint16_t *dst, uint16_t *dst_lo = nullptr, int et = ET_BF16, float scale = 1.0f);
 // f32-grade split-bf16 kernel of the f32x precision mode (kernels_tdnn_x3.hip): f32 activations, hi / lo weight fragments
 bool tdnn_x3_supported(const TdnnKernelParams &p);
 bool tdnn_x3_pool_supported(const TdnnKernelParams &p);      // fused statistics pooling (128-row tiles, plain epilogue)
@@ -276,7 +264,6 @@ bool tdnn_x3m_supported(const TdnnKernelParams &p);
 int launch_tdnn_x3m(const TdnnKernelParams &p, hipStream_t s);
 bool tdnn_x3m_image_in_supported(const TdnnKernelParams &p);
 bool tdnn_x3m_image_out_supported(const TdnnKernelParams &p);
-size_t tdnn_weight_frag_elems(int cout_pad, int cin_pad, int n_taps);
 int launch_stats_pool(const PoolKernelParams &p, int segments, int et, hipStream_t s);
 // second half of the fused pooling: adds each segment's half-tile partials in row order, adds the BN shift
 // back to the mean and writes mean || std like stats_pool_kernel
@@ -369,8 +356,6 @@ struct ConvTapsParams {
   int ldx, ldy, rows, cin_pad, cout_store, nf_total, n_taps, halo_pad, relu;
   int off[ASV_GRID_CONV_MAX_TAPS];           // row offsets dt * pitch + df, in table order
 };
-size_t grid_conv_taps_frag_bytes(int cin_pad, int nf_total, int n_taps, int et);
-void pack_grid_conv_taps(const float *w, int out_ch, int in_ch, int n_taps, int cin_pad, int nf_total, int et, void *dst);
 int launch_grid_conv_taps(const ConvTapsParams &p, int et, hipStream_t s);
 
 // float64 score matrices of the PLDA back-end (kernels_score_matrix.hip): C[i][j] = sum_k A[i][k] B[j][k] + row[i] + col[j] on the f64
@@ -390,9 +375,6 @@ int launch_two_cov_prep(const float *x, int n, int dim, const double *xl, const 
 int score_matrix_valu_f32(const double *A, int m, const double *B, int n, int kp, const double *row, double *scratch, float *C, hipStream_t s);
 #endif
 
-// weight packing (host): dense checkpoint kernel -> [cout_pad][n_taps][cin_pad] in element type
-void pack_tdnn_weight(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps,
-                      int n_taps, int cout_pad, int cin_pad, int et, void *dst);
-// f32 <-> bf16 / IEEE half on the host: host_convert.h
+// weight packing (host): weight_pack.h; f32 <-> bf16 / IEEE half on the host: host_convert.h
 
 }  // namespace asv

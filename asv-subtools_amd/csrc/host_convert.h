@@ -6,6 +6,12 @@
 
 namespace asv {
 
+// Element type of frames-domain storage and of the matrix operands: the launchers' `et` argument (a former `bool bf16`
+// converts to the first two values).
+enum : int { ET_F32 = 0, ET_BF16 = 1, ET_F16 = 2 };
+
+static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
 inline uint16_t f32_to_bf16_host(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);

@@ -734,9 +734,6 @@ bool grid_conv_narrow_supported(const TdnnKernelParams &p, int et) {
   return true;
 }
 
-// elements of the fragment-ordered weight copy for this kernel
-size_t grid_conv_frag_elems(int cin_pad, int cout_pad32, int n_taps) { return (size_t)n_taps * (cin_pad / 16) * (cout_pad32 / 32) * 512; }
-
 int launch_grid_conv_narrow(const TdnnKernelParams &p0, hipStream_t s, bool *persistent) {
   TdnnKernelParams p = p0;
   static const bool live = getenv("ASV_AMD_LIVE_TUNE") != nullptr;

@@ -16,7 +16,7 @@
 //     split.  Two images: the loads of chunk c + 1 are issued at the top of chunk c's K loop - BEHIND the first weight prefetch,
 //     the vector-memory counter retires in order - and converted behind it; one barrier per chunk;
 //   * weights: hi / lo halves in fragment order [chunk][tap][k-group][n-fragment][hi | lo][lane][8], scaled by a power of two
-//     per layer on the host (runtime.hip x3_weight_scale), 1 KiB wave loads from L2 one (tap, k-group) step ahead;
+//     per layer on the host (weight_pack.cpp x3_weight_scale), 1 KiB wave loads from L2 one (tap, k-group) step ahead;
 //   * a unit = one (NFW = 2) or two (NFW = 1) row fragments: 2 or 4 ds_read_b128 feed 6 matrix instructions; the next unit's
 //     reads are issued in front of them;
 //   * epilogue: acc / scale + bias -> [ReLU] -> folded BN, through a per-wave LDS tile to 16-byte stores of whole row pieces.
@@ -25,7 +25,6 @@
 #include <cstdlib>
 
 #include "lds_dma.h"
-#include "host_convert.h"
 
 namespace asv {
 namespace {
@@ -886,33 +885,6 @@ bool grid_conv_x3_shape_ok(int cin_pad, int cout_store) {
   if (cin_pad % QCH != 0 || cin_pad < QCH) return false;
   if (cout_store == 32) return cin_pad == 32;
   return cout_store == 64 || cout_store == 128 || (cout_store > 0 && cout_store % 256 == 0);
-}
-
-size_t grid_conv_x3_frag_elems(int cin_pad, int cout_store, int n_taps) {
-  return (size_t)(cin_pad / QCH) * n_taps * 2 * (cout_store / 32) * 2 * 512;
-}
-
-// [chunk][tap][k-group][n-fragment][hi | lo][lane = (k half lh, channel lr)][8]: channel nf * 32 + lr, k = chunk * 32 + kg * 16 + lh * 8 + e;
-// every weight multiplied by `scale` (a power of two) first; lo = w * scale - hi
-void pack_grid_conv_x3_frags(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps, int cin_pad, int cout_store,
-                             int et, float scale, uint16_t *dst) {
-  const int nft = cout_store / 32;
-  const size_t n = grid_conv_x3_frag_elems(cin_pad, cout_store, n_taps);
-  for (size_t i = 0; i < n; ++i) dst[i] = 0;
-  for (int co = 0; co < out_ch; ++co)
-    for (int t = 0; t < n_taps; ++t) {
-      const int k = taps[t] - left_ctx;
-      for (int ci = 0; ci < in_ch; ++ci) {
-        const int c = ci / QCH, kg = (ci % QCH) / 16, lh = (ci % 16) / 8, e = ci % 8, nf = co / 32, lr = co % 32;
-        const size_t frag = ((((size_t)c * n_taps + t) * 2 + kg) * nft + nf) * 2;
-        const size_t at = (size_t)(lh * 32 + lr) * 8 + e;
-        const float v = w[((size_t)co * in_ch + ci) * tot_ctx + k] * scale;
-        const uint16_t h = et == ET_F16 ? f32_to_f16_host(v) : f32_to_bf16_host(v);
-        const float hv = et == ET_F16 ? f16_to_f32_host(h) : bf16_to_f32_host(h);
-        dst[frag * 512 + at] = h;
-        dst[(frag + 1) * 512 + at] = et == ET_F16 ? f32_to_f16_host(v - hv) : f32_to_bf16_host(v - hv);
-      }
-    }
 }
 
 bool grid_conv_x3_supported(const TdnnKernelParams &p) {

@@ -9,7 +9,7 @@
 // 64 16-bit channels) the activation window - 128 rows + the layer's halo on either side, at most 2 x 168 - is staged in LDS ONCE
 // through the LDS-DMA (lds_dma.h glds16) and every tap reads it shifted: 16-byte slot s of window row w sits at lds_swz(w, s), so
 // the 32 consecutive rows a fragment read touches spread over all banks whatever the shift.  The weights come from global memory
-// (L2) in matrix-fragment order, packed by pack_grid_conv_taps at add time.
+// (L2) in matrix-fragment order, packed by pack_grid_conv_taps (weight_pack.cpp) at add time.
 //
 // Accumulation order (fixed, a property of the kernel and never of the batch): chunk outermost, taps in table order, the four
 // slot pairs of the chunk, and inside the matrix instruction.  Element types: bf16 / f16 rows on mfma_f32_32x32x16_*; f32 rows on
@@ -20,7 +20,6 @@
 #include <cstdlib>
 
 #include "lds_dma.h"
-#include "host_convert.h"
 
 namespace asv {
 namespace {
@@ -135,29 +134,6 @@ int launch_et(const ConvTapsParams &p, hipStream_t s) {
 }
 
 }  // namespace
-
-size_t grid_conv_taps_frag_bytes(int cin_pad, int nf_total, int n_taps, int et) {
-  const int chunk_ch = et == ET_F32 ? 32 : 64;
-  return (size_t)((cin_pad + chunk_ch - 1) / chunk_ch) * n_taps * 4 * nf_total * 1024;
-}
-
-// dense host weight w [out_ch][in_ch][n_taps] -> fragments [chunk][tap][slot pair q][32-channel fragment n][lane = (slot half lh, channel lr)][16 bytes]:
-// the 4 f32 / 8 16-bit input channels chunk * (32 | 64) + (2 q + lh) * (4 | 8) + e of output channel n * 32 + lr; zeros beyond the real channels
-void pack_grid_conv_taps(const float *w, int out_ch, int in_ch, int n_taps, int cin_pad, int nf_total, int et, void *dst) {
-  const int per = et == ET_F32 ? 4 : 8, chunk_ch = per * 8;
-  memset(dst, 0, grid_conv_taps_frag_bytes(cin_pad, nf_total, n_taps, et));
-  for (int co = 0; co < out_ch; ++co)
-    for (int ci = 0; ci < in_ch; ++ci) {
-      const int c = ci / chunk_ch, slot = (ci % chunk_ch) / per, e = ci % per;
-      const int q = slot / 2, lh = slot % 2, n = co / 32, lr = co % 32;
-      for (int t = 0; t < n_taps; ++t) {
-        const size_t elem = ((((size_t)(c * n_taps + t) * 4 + q) * nf_total + n) * 64 + (size_t)(lh * 32 + lr)) * per + e;
-        const float v = w[((size_t)co * in_ch + ci) * n_taps + t];
-        if (et == ET_F32) reinterpret_cast<float *>(dst)[elem] = v;
-        else reinterpret_cast<uint16_t *>(dst)[elem] = et == ET_F16 ? f32_to_f16_host(v) : f32_to_bf16_host(v);
-      }
-    }
-}
 
 int launch_grid_conv_taps(const ConvTapsParams &p, int et, hipStream_t s) {
   ASV_REQUIRE(p.rows % TBM == 0 && p.halo_pad % 8 == 0 && p.halo_pad >= 0 && p.halo_pad <= kConvTapsMaxHalo, "grid_conv_taps: rows %d / window halo %d", p.rows, p.halo_pad);

@@ -1,5 +1,5 @@
-// Host runtime of libasv_amd.so: the layer-program builder (asv_net_*), weight packing,
-// the per-batch segment/row planner and the launch sequencer behind asv_net_extract().
+// Host runtime of libasv_amd.so: the layer-program builder (asv_net_*), the per-batch segment/row planner
+// and the launch sequencer behind asv_net_extract().  (The weight layouts: weight_pack.cpp.)
 //
 // Replaces, for the batched device path, what `for_extract_embedding` +
 // `<Model>.extract_embedding` do one utterance at a time in the reference
@@ -16,7 +16,7 @@
 
 #include <atomic>
 #include "asv_internal.h"
-#include "host_convert.h"
+#include "weight_pack.h"
 
 namespace asv {
 
@@ -29,115 +29,6 @@ void set_error(const char *fmt, ...) {
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
   g_last_error = buf;
-}
-
-static uint16_t f32_to_h16_host(float f, int et) { return et == ET_F16 ? f32_to_f16_host(f) : f32_to_bf16_host(f); }
-static float h16_to_f32_host(uint16_t h, int et) { return et == ET_F16 ? f16_to_f32_host(h) : bf16_to_f32_host(h); }
-
-void pack_tdnn_weight(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps,
-                      int cout_pad, int cin_pad, int et, void *dst) {
-  const size_t n = (size_t)cout_pad * n_taps * cin_pad;
-  if (et != ET_F32) memset(dst, 0, n * 2); else memset(dst, 0, n * 4);
-  for (int co = 0; co < out_ch; ++co)
-    for (int t = 0; t < n_taps; ++t) {
-      const int k = taps[t] - left_ctx;
-      const size_t base = ((size_t)co * n_taps + t) * cin_pad;
-      for (int ci = 0; ci < in_ch; ++ci) {
-        const float v = w[((size_t)co * in_ch + ci) * tot_ctx + k];
-        if (et != ET_F32) reinterpret_cast<uint16_t *>(dst)[base + ci] = f32_to_h16_host(v, et);
-        else reinterpret_cast<float *>(dst)[base + ci] = v;
-      }
-    }
-}
-
-size_t tdnn_weight_frag_elems(int cout_pad, int cin_pad, int n_taps) {
-  return (size_t)cout_pad * n_taps * round_up(cin_pad, 64);
-}
-
-// MFMA-fragment order for kernels_tdnn_v3.hip: [n_frag32][tap][chunk64][k_group16][lane][8];
-// lane = (k half lh, channel lr): channel n_frag*32 + lr, k = chunk*64 + k_group*16 + lh*8 + e.
-// et: ET_BF16 / ET_F16 = the 16-bit type of the fragments.  dst_lo (the f32x mode): the second halves w * scale - hi;
-// `scale` (a power of two, exact) multiplies every weight first - the half-precision split uses it to lift the weights of a
-// layer into the upper part of the half range, where hi AND lo are normal numbers (22 significant bits together); the
-// kernel's epilogue multiplies the accumulator by 1 / scale (exact).
-void pack_tdnn_weight_frags(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps,
-                            int cout_pad, int cin_pad, uint16_t *dst, uint16_t *dst_lo, int et, float scale) {
-  const int nchunks = round_up(cin_pad, 64) / 64;
-  memset(dst, 0, tdnn_weight_frag_elems(cout_pad, cin_pad, n_taps) * 2);
-  if (dst_lo) memset(dst_lo, 0, tdnn_weight_frag_elems(cout_pad, cin_pad, n_taps) * 2);
-  for (int co = 0; co < out_ch; ++co) {
-    const int nf = co / 32, lr = co % 32;
-    for (int t = 0; t < n_taps; ++t) {
-      const int k = taps[t] - left_ctx;
-      for (int ci = 0; ci < in_ch; ++ci) {
-        const int c = ci / 64, kg = (ci % 64) / 16, lh = (ci % 16) / 8, e = ci % 8;
-        const size_t idx = ((((size_t)nf * n_taps + t) * nchunks + c) * 4 + kg) * 512 + (size_t)(lh * 32 + lr) * 8 + e;
-        const float v = w[((size_t)co * in_ch + ci) * tot_ctx + k] * scale;
-        dst[idx] = f32_to_h16_host(v, et);
-        if (dst_lo) dst_lo[idx] = f32_to_h16_host(v - h16_to_f32_host(dst[idx], et), et);      // f32x mode: w = hi + lo
-      }
-    }
-  }
-}
-
-// Plain order for kernels_tdnn_p8x.hip (the weight half-tiles arrive by LDS-DMA, 128-byte rows): [cout_pad][tap][chunk32][hi 32 | lo 32],
-// the same halves of w * scale as pack_tdnn_weight_frags writes (the two kernels give the same bits)
-void pack_tdnn_weight_x3p(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps, int cout_pad, int cin_pad,
-                          int et, float scale, uint16_t *dst) {
-  const int nchunks = cin_pad / 32;
-  memset(dst, 0, (size_t)cout_pad * n_taps * nchunks * 64 * 2);
-  for (int co = 0; co < out_ch; ++co)
-    for (int t = 0; t < n_taps; ++t) {
-      const int k = taps[t] - left_ctx;
-      for (int ci = 0; ci < in_ch; ++ci) {
-        const size_t idx = (((size_t)co * n_taps + t) * nchunks + ci / 32) * 64 + ci % 32;
-        const float v = w[((size_t)co * in_ch + ci) * tot_ctx + k] * scale;
-        dst[idx] = f32_to_h16_host(v, et);
-        dst[idx + 32] = f32_to_h16_host(v - h16_to_f32_host(dst[idx], et), et);
-      }
-    }
-}
-
-// 8-bit fragments of the f32m form (kernels_tdnn_chainm.hip / kernels_tdnn_x3m.hip, the scaled 8-bit matrix instruction): for the halves
-// hi = half(w * scale), lo = w * scale - hi that pack_tdnn_weight_frags splits into, two planes of
-// [32-channel output fragment][tap][32-channel input group][lane = (lh, output channel lr)][16]: plane 0 = e4m3(lo 2^6) (|lo| <= 2^-11 |hi|,
-// hi < 2^14 under x3_weight_scale), plane 1 = e4m3(hi 2^-6).  Byte q of lane half lh = input channel 32 group + (q < 8 ? 8 lh + q :
-// 16 + 8 lh + q - 8) - the channels the lane's two half fragments of the group hold, in their order, so that a kernel may also MAKE plane 1
-// from those half fragments in registers (v_cvt_scalef32_pk_fp8_f16: kernels_tdnn_x3m.hip does; the chain kernel kernels_tdnn_chainm.hip
-// fetches it - 24 conversions per K step cost its waves more issue time than two more 16-byte loads, profiles/r6s_*).  The kernels' block
-// scales undo the 2^6 / 2^-6.
-size_t tdnn_weight_mx8_plane_bytes(int cout_pad, int cin_pad, int n_taps) { return (size_t)(cout_pad / 32) * n_taps * ((cin_pad + 31) / 32) * 1024; }
-size_t tdnn_weight_mx8_bytes(int cout_pad, int cin_pad, int n_taps) { return 2 * tdnn_weight_mx8_plane_bytes(cout_pad, cin_pad, n_taps); }
-void pack_tdnn_weight_mx8(const float *w, int out_ch, int in_ch, int tot_ctx, int left_ctx, const int *taps, int n_taps, int cout_pad, int cin_pad,
-                          float scale, uint8_t *dst) {
-  const int ngroups = (cin_pad + 31) / 32;                    // (a last, partial group is zero-padded: e4m3(0) = 0)
-  memset(dst, 0, tdnn_weight_mx8_bytes(cout_pad, cin_pad, n_taps));
-  const size_t plane = tdnn_weight_mx8_plane_bytes(cout_pad, cin_pad, n_taps);
-  for (int co = 0; co < out_ch; ++co) {
-    const int nf = co / 32, lr = co % 32;
-    for (int t = 0; t < n_taps; ++t) {
-      const int k = taps[t] - left_ctx;
-      for (int ci = 0; ci < in_ch; ++ci) {
-        const int g = ci / 32, r = ci % 32, kg = r / 16, lh = (r % 16) / 8, q = kg * 8 + r % 8;
-        const float v = w[((size_t)co * in_ch + ci) * tot_ctx + k] * scale;
-        const float hi = f16_to_f32_host(f32_to_f16_host(v));
-        const size_t at = (((size_t)nf * n_taps + t) * ngroups + g) * 1024 + (size_t)(lh * 32 + lr) * 16 + q;
-        dst[at] = f32_to_e4m3_host((v - hi) * 64.0f);
-        dst[plane + at] = f32_to_e4m3_host(hi * (1.0f / 64.0f));
-      }
-    }
-  }
-}
-
-// Power of two that lifts the largest weight of a layer to [2^13, 2^14) (the half-precision split of the f32x mode): every
-// weight down to 2^-15 of the largest keeps a normal lo half; the products grow by the same factor, far inside f32.
-static float x3_weight_scale(const float *w, size_t n) {
-  float mx = 0.0f;
-  for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
-  if (!(mx > 0.0f) || !std::isfinite(mx)) return 1.0f;
-  int e = 0;
-  (void)std::frexp(mx, &e);                       // mx = m * 2^e, 0.5 <= m < 1
-  return std::ldexp(1.0f, 14 - e);
 }
 
 namespace {
@@ -286,13 +177,73 @@ int dev_upload(asv_net *net, const void *host, size_t bytes, void **out) {
   return ASV_OK;
 }
 
+template <class T>
+int upload_vec(asv_net *net, const std::vector<T> &v, void **out) { return dev_upload(net, v.data(), v.size() * sizeof(T), out); }
+
 int upload_padded(asv_net *net, const float *src, int n, int n_pad, float fill, float **out) {
   std::vector<float> tmp((size_t)n_pad, fill);
   if (src) memcpy(tmp.data(), src, (size_t)n * sizeof(float));
   void *d = nullptr;
-  int rc = dev_upload(net, tmp.data(), tmp.size() * sizeof(float), &d);
+  int rc = upload_vec(net, tmp, &d);
   *out = reinterpret_cast<float *>(d);
   return rc;
+}
+
+// A layer's weights in the fragment forms the wide frame kernels and the layer chains read (kernels_tdnn_v3.hip order): the 16-bit
+// fragments alone, or - with_lo, the f32x mode - the hi / lo halves of w * s.scale, and - with_mx8, the f32m form - their 8-bit planes
+struct FragForms { std::vector<uint16_t> hi, lo; std::vector<uint8_t> w8; };
+FragForms pack_frag_forms(const TapWeights &s, int cout_pad, int cin_pad, int et, bool with_lo, bool with_mx8) {
+  FragForms f;
+  f.hi.resize(tdnn_weight_frag_elems(cout_pad, cin_pad, s.n_taps));
+  f.lo.resize(with_lo ? f.hi.size() : 0);
+  pack_tdnn_weight_frags(s.w, s.out_ch, s.in_ch, s.tot_ctx, s.left_ctx, s.taps, s.n_taps, cout_pad, cin_pad, f.hi.data(), with_lo ? f.lo.data() : nullptr, et, s.scale);
+  if (with_mx8) f.w8 = pack_tdnn_weight_mx8(s, cout_pad, cin_pad);
+  return f;
+}
+
+// Which weight layouts a TDNN layer gets, besides the plain order every layer has (asv_net_add_tdnn packs and uploads one per field).
+struct TdnnPacks { bool frags16, x3_frags, mx8, x3p, conv2d, conv2d_x3, utts_split, chain_host_copies; };
+TdnnPacks tdnn_packs_for(const asv_net *net, const asv_tdnn_desc_t &d, int dom, const Op &op) {
+  const int kind = net->domains[dom].kind;
+  const bool h16 = net->dom_et(dom) != ET_F32;     // 16-bit rows and weights (bf16 or half)
+  TdnnPacks n;
+  // the two fragment orders are mutually exclusive per layer: a 3x3 trunk convolution the conv2d kernels take never needs
+  // the v3 order (grid_conv_* precede big3 in the dispatch and accept every such layer), and each family has its own pointer
+  // (+ the 32 -> 64 stride-2 convolution in space-to-depth form: 4 x 32 input channels, 4 taps, 64 output channels)
+  const bool s2d = h16 && kind == 2 && d.n_taps == 4 && op.cin_pad == 128 && d.in_ch == 128 && d.out_ch == 64;
+  // 3x3 trunk convolutions with 32 / 64 / 128 / 256 channels: fragment order of kernels_conv2d.hip
+  n.conv2d = s2d || (h16 && kind == 2 && d.n_taps == 9 && (op.cin_pad == 32 || op.cin_pad == 64 || op.cin_pad == 128 || op.cin_pad == 256) &&
+                     d.in_ch == op.cin_pad && d.out_ch == d.in_ch);
+  n.frags16 = h16 && !n.conv2d && op.cout_store > 96 && op.cin_pad >= 64;         // candidates of the 256- / 128-channel tiles (kernels_tdnn_v3.hip)
+  // f32x mode: hi / lo halves of the weights in the same fragment order (kernels_tdnn_x3.hip)
+  n.x3_frags = net->x3() && !op.utts && kind == ASV_DOMAIN_FRAMES && op.cout_store >= 192 && op.cin_pad >= 32;
+  n.mx8 = n.x3_frags && net->x3_mx() && op.cout_pad % 32 == 0;
+  // the candidates of the 8-phase form (256 x 256 tiles; the dispatch decides per batch): the plain epilogue, whole 32-channel chunks
+  const bool plain = (d.act1 == ASV_ACT_NONE || d.act1 == ASV_ACT_RELU) && d.act2 == ASV_ACT_NONE && !d.affine_first;
+  n.x3p = n.x3_frags && plain && op.cin_pad % 32 == 0 && d.in2_buf < 0 && d.seg_bias_buf < 0 && d.seg_scale_buf < 0 && d.res_buf < 0 && (long long)op.cin_pad * d.n_taps >= 512;
+  // f32x mode, grid domain (the 2-D ResNet trunk) and the frames-domain layers the wide split kernel does not take (fewer than
+  // 192 output channels, or a second input): hi / lo halves in the fragment order of kernels_conv2d_x3.hip, scaled by the
+  // layer's power of two for the half-precision split
+  n.conv2d_x3 = net->x3() && !op.utts && (kind == 2 || !(n.x3_frags && d.in2_buf < 0)) && grid_conv_x3_shape_ok(op.cin_pad, op.cout_store) &&
+                (net->flags & ASV_FLAG_SMALL_TILES) == 0;
+  // pooled-domain layers keep f32 activations; their GEMM runs on the bf16 matrix cores with every operand split into two bf16
+  // halves, the weight halves in the fragment order kernels_utts.hip walks
+  n.utts_split = op.utts && net->frames_h16();
+  // possible member of a layer chain (it has fragments): its BatchNorm may be folded into the next member, or the previous member's into it
+  n.chain_host_copies = (n.frags16 || n.x3_frags) && kind == ASV_DOMAIN_FRAMES && (net->flags & (ASV_FLAG_NO_FUSE | ASV_FLAG_NO_CHAIN)) == 0;
+  return n;
+}
+
+// possible member of a layer chain: the host copies asv_net_finalize folds BatchNorms with (the previous member's into this layer, this one's into the next)
+void keep_chain_host_copies(Op &op, const asv_tdnn_desc_t &d) {
+  if (d.scale) { op.host_scale.assign(d.scale, d.scale + d.out_ch); op.host_shift.assign(d.shift, d.shift + d.out_ch); }
+  if (d.n_taps == 1 && d.taps[0] == 0 && d.in_ch == kChainWidth) {
+    const size_t tot = (size_t)d.w_tot_context, k = (size_t)(0 - d.w_left_context);
+    op.host_w.resize((size_t)d.out_ch * d.in_ch);
+    for (size_t i = 0; i < op.host_w.size(); ++i) op.host_w[i] = d.weight[i * tot + k];           // the one active tap, [out][in]
+    op.host_bias.assign((size_t)d.out_ch, 0.0f);
+    if (d.bias) op.host_bias.assign(d.bias, d.bias + d.out_ch);
+  }
 }
 
 int check_view(const asv_net *net, int buf, int ch_off, int ch, const char *what) {
@@ -559,104 +510,34 @@ int asv_net_add_tdnn(asv_net_t *net, const asv_tdnn_desc_t *d) {
   ASV_REQUIRE((d->scale == nullptr) == (d->shift == nullptr), "tdnn: scale and shift come together");
   for (int a : {d->act1, d->act2}) ASV_REQUIRE(a >= ASV_ACT_NONE && a <= ASV_ACT_SIGMOID, "tdnn: unknown activation %d", a);
 
-  Op op;
-  op.kind = OP_TDNN;
-  op.tdnn = *d;
-  op.utts = net->is_utts(dom);
+  Op op; op.kind = OP_TDNN; op.tdnn = *d; op.utts = net->is_utts(dom);
   const int et = net->dom_et(dom);
-  const bool bf16 = et != ET_F32;                  // 16-bit rows and weights (bf16 or half)
   op.cin_pad = round_up(d->in_ch, kChanAlign);
   op.cout_pad = round_up(d->out_ch, kBigTileN);
   op.cout_store = round_up(d->out_ch, kChanAlign);
   ASV_REQUIRE(d->out_ch_off + op.cout_store <= net->bufs[d->out_buf].ld, "tdnn: padded output view exceeds the buffer pitch");
   ASV_ON_DEVICE(net->device);
-  {
-    const size_t n = (size_t)op.cout_pad * d->n_taps * op.cin_pad;
-    std::vector<unsigned char> packed(n * (bf16 ? 2 : 4));
-    pack_tdnn_weight(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cout_pad,
-                     op.cin_pad, et, packed.data());
-    if ((rc = dev_upload(net, packed.data(), packed.size(), &op.w))) return rc;
-    // the two fragment orders are mutually exclusive per layer: a 3x3 trunk convolution the conv2d kernels take never needs
-    // the v3 order (grid_conv_* precede big3 in the dispatch and accept every such layer), and each family has its own pointer
-    // (+ the 32 -> 64 stride-2 convolution in space-to-depth form: 4 x 32 input channels, 4 taps, 64 output channels)
-    const bool s2d_pack = bf16 && net->domains[dom].kind == 2 && d->n_taps == 4 && op.cin_pad == 128 && d->in_ch == 128 && d->out_ch == 64;
-    const bool conv2d_pack = s2d_pack || (bf16 && net->domains[dom].kind == 2 && d->n_taps == 9 && (op.cin_pad == 32 || op.cin_pad == 64 || op.cin_pad == 128 || op.cin_pad == 256) &&
-                             d->in_ch == op.cin_pad && d->out_ch == d->in_ch);
-    if (bf16 && !conv2d_pack && op.cout_store > 96 && op.cin_pad >= 64) {         // candidates of the 256- / 128-channel tiles (kernels_tdnn_v3.hip)
-      std::vector<uint16_t> frags(tdnn_weight_frag_elems(op.cout_pad, op.cin_pad, d->n_taps));
-      pack_tdnn_weight_frags(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cout_pad, op.cin_pad, frags.data(), nullptr, et);
-      if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &op.wfrag))) return rc;
-    }
-    if (net->x3() && !op.utts && net->domains[dom].kind == ASV_DOMAIN_FRAMES && op.cout_store >= 192 && op.cin_pad >= 32) {
-      // f32x mode: hi / lo halves of the weights in the same fragment order (kernels_tdnn_x3.hip); the half-precision split
-      // scales the layer's weights by a power of two first (see x3_weight_scale)
-      std::vector<uint16_t> hi(tdnn_weight_frag_elems(op.cout_pad, op.cin_pad, d->n_taps)), lo(hi.size());
-      op.w_scale = net->x3_et() == ET_F16 ? x3_weight_scale(d->weight, (size_t)d->out_ch * d->in_ch * d->w_tot_context) : 1.0f;
-      pack_tdnn_weight_frags(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cout_pad, op.cin_pad, hi.data(), lo.data(),
-                             net->x3_et(), op.w_scale);
-      if ((rc = dev_upload(net, hi.data(), hi.size() * 2, &op.wfrag))) return rc;
-      if ((rc = dev_upload(net, lo.data(), lo.size() * 2, &op.wlo))) return rc;
-      if (net->x3_mx() && op.cout_pad % 32 == 0) {
-        std::vector<uint8_t> w8(tdnn_weight_mx8_bytes(op.cout_pad, op.cin_pad, d->n_taps));
-        pack_tdnn_weight_mx8(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cout_pad, op.cin_pad, op.w_scale, w8.data());
-        if ((rc = dev_upload(net, w8.data(), w8.size(), &op.w8))) return rc;
-      }
-      // the candidates of the 8-phase form (256 x 256 tiles; the dispatch decides per batch): the plain epilogue, whole 32-channel chunks
-      const bool plain = (d->act1 == ASV_ACT_NONE || d->act1 == ASV_ACT_RELU) && d->act2 == ASV_ACT_NONE && !d->affine_first;
-      if (plain && op.cin_pad % 32 == 0 && d->in2_buf < 0 && d->seg_bias_buf < 0 && d->seg_scale_buf < 0 && d->res_buf < 0 && (long long)op.cin_pad * d->n_taps >= 512) {
-        std::vector<uint16_t> rows((size_t)op.cout_pad * d->n_taps * (op.cin_pad / 32) * 64);
-        pack_tdnn_weight_x3p(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cout_pad, op.cin_pad, net->x3_et(), op.w_scale,
-                             rows.data());
-        if ((rc = dev_upload(net, rows.data(), rows.size() * 2, &op.wx3p))) return rc;
-      }
-    }
-    const bool x3_wide_frames = net->x3() && !op.utts && net->domains[dom].kind == ASV_DOMAIN_FRAMES && op.cout_store >= 192 && op.cin_pad >= 32 && d->in2_buf < 0;
-    if (net->x3() && !op.utts && (net->domains[dom].kind == 2 || !x3_wide_frames) && grid_conv_x3_shape_ok(op.cin_pad, op.cout_store) &&
-        (net->flags & ASV_FLAG_SMALL_TILES) == 0) {
-      // f32x mode, grid domain (the 2-D ResNet trunk) and the frames-domain layers the wide split kernel does not take (fewer than
-      // 192 output channels, or a second input): hi / lo halves in the fragment order of kernels_conv2d_x3.hip, scaled by the
-      // layer's power of two for the half-precision split
-      std::vector<uint16_t> frags(grid_conv_x3_frag_elems(op.cin_pad, op.cout_store, d->n_taps));
-      op.w_scale = net->x3_et() == ET_F16 ? x3_weight_scale(d->weight, (size_t)d->out_ch * d->in_ch * d->w_tot_context) : 1.0f;
-      pack_grid_conv_x3_frags(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cin_pad, op.cout_store, net->x3_et(),
-                              op.w_scale, frags.data());
-      if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &op.wconv))) return rc;
-    }
-    if (conv2d_pack) {
-      // 3x3 trunk convolutions with 32 / 64 channels: fragment order of kernels_conv2d.hip,
-      // [tap][k-group][n-fragment][lane = (k half lh, channel lr)][8], k = kg * 16 + lh * 8 + e
-      const int kgs = op.cin_pad / 16, nfs = (d->out_ch + 31) / 32;
-      std::vector<uint16_t> frags(grid_conv_frag_elems(op.cin_pad, nfs * 32, d->n_taps), 0);
-      for (int t = 0; t < d->n_taps; ++t) {
-        const int k = d->taps[t] - d->w_left_context;
-        for (int co = 0; co < d->out_ch; ++co)
-          for (int ci = 0; ci < d->in_ch; ++ci) {
-            const int kg = ci / 16, lh = (ci % 16) / 8, e = ci % 8, nf = co / 32, lr = co % 32;
-            frags[((size_t)(t * kgs + kg) * nfs + nf) * 512 + (size_t)(lh * 32 + lr) * 8 + e] =
-                f32_to_h16_host(d->weight[((size_t)co * d->in_ch + ci) * d->w_tot_context + k], et);
-          }
-      }
-      if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &op.wconv))) return rc;
-    }
-    if (op.utts && net->frames_h16()) {
-      // pooled-domain layers keep f32 activations; their GEMM runs on the bf16 matrix cores with every
-      // operand split into two bf16 halves, the weight halves in the fragment order kernels_utts.hip walks:
-      // [32-channel fragment][32-k step][j][lane = (k half lh, channel lr)][8], k = 32 * step + 16 * lh + 8 * j + e
-      const float *wf = reinterpret_cast<const float *>(packed.data());
-      const int ksteps = (op.cin_pad + 31) / 32;
-      const size_t nfrag = (size_t)(op.cout_pad / 32) * ksteps * 1024;
-      std::vector<uint16_t> hi(nfrag, 0), lo(nfrag, 0);
-      for (int co = 0; co < d->out_ch; ++co)
-        for (int ci = 0; ci < d->in_ch; ++ci) {
-          const float v = wf[(size_t)co * op.cin_pad + ci];
-          const int r = ci % 32;
-          const size_t idx = (((size_t)(co / 32) * ksteps + ci / 32) * 2 + (r % 16) / 8) * 512 + (size_t)((r / 16) * 32 + co % 32) * 8 + r % 8;
-          hi[idx] = f32_to_bf16_host(v);
-          lo[idx] = f32_to_bf16_host(v - bf16_to_f32_host(hi[idx]));
-        }
-      if ((rc = dev_upload(net, hi.data(), nfrag * 2, &op.wfrag))) return rc;
-      if ((rc = dev_upload(net, lo.data(), nfrag * 2, &op.wlo))) return rc;
-    }
+  const TdnnPacks need = tdnn_packs_for(net, *d, dom, op);
+  // the half-precision split of the f32x mode scales the layer's weights by a power of two first (see x3_weight_scale)
+  if ((need.x3_frags || need.conv2d_x3) && net->x3_et() == ET_F16) op.w_scale = x3_weight_scale(d->weight, (size_t)d->out_ch * d->in_ch * d->w_tot_context);
+  const TapWeights tw{d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps};
+  const TapWeights tws{tw.w, tw.out_ch, tw.in_ch, tw.tot_ctx, tw.left_ctx, tw.taps, tw.n_taps, op.w_scale};      // for the split layouts
+  std::vector<unsigned char> packed(tdnn_weight_bytes(op.cout_pad, op.cin_pad, d->n_taps, et));
+  pack_tdnn_weight(d->weight, d->out_ch, d->in_ch, d->w_tot_context, d->w_left_context, d->taps, d->n_taps, op.cout_pad, op.cin_pad, et, packed.data());
+  if ((rc = upload_vec(net, packed, &op.w))) return rc;
+  if (need.frags16 && (rc = upload_vec(net, pack_frag_forms(tw, op.cout_pad, op.cin_pad, et, false, false).hi, &op.wfrag))) return rc;
+  if (need.x3_frags) {
+    const FragForms f = pack_frag_forms(tws, op.cout_pad, op.cin_pad, net->x3_et(), true, need.mx8);
+    if ((rc = upload_vec(net, f.hi, &op.wfrag)) || (rc = upload_vec(net, f.lo, &op.wlo))) return rc;
+    if (need.mx8 && (rc = upload_vec(net, f.w8, &op.w8))) return rc;
+  }
+  if (need.x3p && (rc = upload_vec(net, pack_tdnn_weight_x3p(tws, op.cout_pad, op.cin_pad, net->x3_et()), &op.wx3p))) return rc;
+  if (need.conv2d_x3 && (rc = upload_vec(net, pack_grid_conv_x3_frags(tws, op.cin_pad, op.cout_store, net->x3_et()), &op.wconv))) return rc;
+  if (need.conv2d && (rc = upload_vec(net, pack_grid_conv_frags(tw, op.cin_pad, et), &op.wconv))) return rc;
+  if (need.utts_split) {
+    std::vector<uint16_t> hi(utts_weight_split_elems(op.cout_pad, op.cin_pad)), lo(hi.size());
+    pack_utts_weight_split(tw, op.cout_pad, op.cin_pad, hi.data(), lo.data());
+    if ((rc = upload_vec(net, hi, &op.wfrag)) || (rc = upload_vec(net, lo, &op.wlo))) return rc;
   }
   if ((rc = upload_padded(net, d->bias, d->out_ch, op.cout_pad, 0.0f, &op.bias))) return rc;
   op.has_affine = d->scale != nullptr;
@@ -664,17 +545,7 @@ int asv_net_add_tdnn(asv_net_t *net, const asv_tdnn_desc_t *d) {
     if ((rc = upload_padded(net, d->scale, d->out_ch, op.cout_pad, 0.0f, &op.scale))) return rc;
     if ((rc = upload_padded(net, d->shift, d->out_ch, op.cout_pad, 0.0f, &op.shift))) return rc;
   }
-  if ((bf16 || net->x3()) && !op.utts && net->domains[dom].kind == ASV_DOMAIN_FRAMES && op.wfrag != nullptr && (net->flags & (ASV_FLAG_NO_FUSE | ASV_FLAG_NO_CHAIN)) == 0) {
-    // possible member of a layer chain: its BatchNorm may be folded into the next member, or the previous member's into it
-    if (d->scale) { op.host_scale.assign(d->scale, d->scale + d->out_ch); op.host_shift.assign(d->shift, d->shift + d->out_ch); }
-    if (d->n_taps == 1 && d->taps[0] == 0 && d->in_ch == kChainWidth) {
-      const size_t tot = (size_t)d->w_tot_context, k = (size_t)(0 - d->w_left_context);
-      op.host_w.resize((size_t)d->out_ch * d->in_ch);
-      for (size_t i = 0; i < op.host_w.size(); ++i) op.host_w[i] = d->weight[i * tot + k];           // the one active tap, [out][in]
-      op.host_bias.assign((size_t)d->out_ch, 0.0f);
-      if (d->bias) op.host_bias.assign(d->bias, d->bias + d->out_ch);
-    }
-  }
+  if (need.chain_host_copies) keep_chain_host_copies(op, *d);
   op.tdnn.weight = nullptr; op.tdnn.bias = nullptr; op.tdnn.scale = nullptr; op.tdnn.shift = nullptr;
   net->ops.push_back(op);
   return ASV_OK;
@@ -789,13 +660,8 @@ int asv_net_add_res2(asv_net_t *net, const asv_res2_desc_t *d) {
   ASV_REQUIRE(d->in_ch_off % 8 == 0 && d->out_ch_off % 8 == 0, "res2: channel offsets must be multiples of 8 (16-byte rows pieces)");
   Op op; op.kind = OP_RES2; op.res2 = *d;
   ASV_ON_DEVICE(net->device);
-  const int W = kRes2Width, tot = 2 * d->dilation + 1;
-  const int taps[3] = {-d->dilation, 0, d->dilation};
-  const size_t per_branch = tdnn_weight_frag_elems(W, W, 3);
-  std::vector<uint16_t> frags(per_branch * d->branches);
-  for (int b = 0; b < d->branches; ++b)
-    pack_tdnn_weight_frags(d->weight + (size_t)b * W * W * tot, W, W, tot, -d->dilation, taps, 3, W, W, frags.data() + per_branch * b, nullptr, net->frames_et());
-  if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &op.wfrag))) return rc;
+  const int W = kRes2Width;
+  if ((rc = upload_vec(net, pack_res2_branch_frags(d->weight, W, d->branches, d->dilation, net->frames_et()), &op.wfrag))) return rc;
   if ((rc = upload_padded(net, d->bias, d->branches * W, d->branches * W, 0.0f, &op.bias))) return rc;
   if ((rc = upload_padded(net, d->scale, d->branches * W, d->branches * W, 0.0f, &op.scale))) return rc;
   if ((rc = upload_padded(net, d->shift, d->branches * W, d->branches * W, 0.0f, &op.shift))) return rc;
@@ -821,13 +687,7 @@ int asv_net_add_res2n(asv_net_t *net, const asv_res2n_desc_t *d) {
   ASV_REQUIRE(d->in_ch_off % 8 == 0 && d->out_ch_off % 8 == 0, "res2n: channel offsets must be multiples of 8 (16-byte row pieces)");
   Op op; op.kind = OP_RES2N; op.res2n = *d;
   ASV_ON_DEVICE(net->device);
-  const int tot = 2 * d->dilation + 1;
-  const int taps[3] = {-d->dilation, 0, d->dilation};
-  const size_t per_branch = tdnn_weight_frag_elems(W, W, 3);
-  std::vector<uint16_t> frags(per_branch * branches);
-  for (int b = 0; b < branches; ++b)
-    pack_tdnn_weight_frags(d->weight + (size_t)b * W * W * tot, W, W, tot, -d->dilation, taps, 3, W, W, frags.data() + per_branch * b, nullptr, net->frames_et());
-  if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &op.wfrag))) return rc;
+  if ((rc = upload_vec(net, pack_res2_branch_frags(d->weight, W, branches, d->dilation, net->frames_et()), &op.wfrag))) return rc;
   if (d->bias != nullptr && (rc = upload_padded(net, d->bias, branches * W, branches * W, 0.0f, &op.bias))) return rc;
   if ((rc = upload_padded(net, d->scale, branches * W, branches * W, 0.0f, &op.scale))) return rc;
   if ((rc = upload_padded(net, d->shift, branches * W, branches * W, 0.0f, &op.shift))) return rc;
@@ -936,7 +796,7 @@ int asv_net_add_grid_conv(asv_net_t *net, const asv_grid_conv_desc_t *d) {
   const int et = net->dom_et(dom);
   std::vector<unsigned char> frags(grid_conv_taps_frag_bytes(cin_pad, nf_total, d->n_taps, et));
   pack_grid_conv_taps(d->weight, d->out_ch, d->in_ch, d->n_taps, cin_pad, nf_total, et, frags.data());
-  if ((rc = dev_upload(net, frags.data(), frags.size(), &op.wconv))) return rc;
+  if ((rc = upload_vec(net, frags, &op.wconv))) return rc;
   if ((rc = upload_padded(net, d->bias, d->bias ? d->out_ch : 0, op.cout_pad, 0.0f, &op.bias))) return rc;
   op.gconv.weight = nullptr; op.gconv.bias = nullptr;
   net->ops.push_back(op);
@@ -1093,35 +953,18 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
         if (!prev.has_affine || prev.host_scale.empty() || cur.host_w.empty()) continue;
         const int out_ch = cur.tdnn.out_ch, in_ch = cur.tdnn.in_ch;
         std::vector<float> wf((size_t)out_ch * in_ch), bf((size_t)cur.cout_pad, 0.0f);
-        for (int co = 0; co < out_ch; ++co) {
-          double acc = cur.host_bias[co];
-          for (int ci = 0; ci < in_ch; ++ci) {
-            const float w = cur.host_w[(size_t)co * in_ch + ci];
-            wf[(size_t)co * in_ch + ci] = w * prev.host_scale[ci];
-            acc += (double)w * (double)prev.host_shift[ci];
-          }
-          bf[co] = (float)acc;
-        }
+        fold_affine_into(cur.host_w.data(), cur.host_bias.data(), prev.host_scale.data(), prev.host_shift.data(), out_ch, in_ch, wf.data(), bf.data());
         const int tap0 = 0;
-        std::vector<uint16_t> frags(tdnn_weight_frag_elems(cur.cout_pad, cur.cin_pad, 1)), frags_lo;
+        if (net->x3() && net->x3_et() == ET_F16) cur.w_scale_fold = x3_weight_scale(wf.data(), wf.size());
+        const TapWeights tw{wf.data(), out_ch, in_ch, 1, 0, &tap0, 1, cur.w_scale_fold};
+        const FragForms f = pack_frag_forms(tw, cur.cout_pad, cur.cin_pad, net->x3() ? net->x3_et() : net->frames_et(), net->x3(), net->x3_mx());
         ASV_ON_DEVICE(net->device);
         int rc;
-        if (net->x3()) {
-          frags_lo.resize(frags.size());
-          cur.w_scale_fold = net->x3_et() == ET_F16 ? x3_weight_scale(wf.data(), wf.size()) : 1.0f;
-          pack_tdnn_weight_frags(wf.data(), out_ch, in_ch, 1, 0, &tap0, 1, cur.cout_pad, cur.cin_pad, frags.data(), frags_lo.data(), net->x3_et(), cur.w_scale_fold);
-          if ((rc = dev_upload(net, frags_lo.data(), frags_lo.size() * 2, &cur.wlo_fold))) return rc;
-          if (net->x3_mx()) {
-            std::vector<uint8_t> w8(tdnn_weight_mx8_bytes(cur.cout_pad, cur.cin_pad, 1));
-            pack_tdnn_weight_mx8(wf.data(), out_ch, in_ch, 1, 0, &tap0, 1, cur.cout_pad, cur.cin_pad, cur.w_scale_fold, w8.data());
-            if ((rc = dev_upload(net, w8.data(), w8.size(), &cur.w8_fold))) return rc;
-          }
-        } else {
-          pack_tdnn_weight_frags(wf.data(), out_ch, in_ch, 1, 0, &tap0, 1, cur.cout_pad, cur.cin_pad, frags.data(), nullptr, net->frames_et());
-        }
-        if ((rc = dev_upload(net, frags.data(), frags.size() * 2, &cur.wfrag_fold))) return rc;
+        if (net->x3() && (rc = upload_vec(net, f.lo, &cur.wlo_fold))) return rc;
+        if (net->x3_mx() && (rc = upload_vec(net, f.w8, &cur.w8_fold))) return rc;
+        if ((rc = upload_vec(net, f.hi, &cur.wfrag_fold))) return rc;
         void *bdev = nullptr;
-        if ((rc = dev_upload(net, bf.data(), bf.size() * sizeof(float), &bdev))) return rc;
+        if ((rc = upload_vec(net, bf, &bdev))) return rc;
         cur.bias_fold = reinterpret_cast<float *>(bdev);
       }
     }

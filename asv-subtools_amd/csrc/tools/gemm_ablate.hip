@@ -5,7 +5,7 @@
 #include <vector>
 #include <algorithm>
 #include "../asv_internal.h"
-#include "../host_convert.h"
+#include "../weight_pack.h"
 
 using namespace asv;
 

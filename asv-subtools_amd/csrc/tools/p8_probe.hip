@@ -9,7 +9,7 @@
 #include <cmath>
 #include <vector>
 #include "../asv_internal.h"
-#include "../host_convert.h"
+#include "../weight_pack.h"
 
 using namespace asv;
 

@@ -54,7 +54,7 @@ def product(x, w):
         return x @ w
     if MODE == "f16":
         return f16(x) @ f16(w)
-    s = 2.0 ** (14 - np.frexp(np.abs(w).max())[1])          # runtime.hip x3_weight_scale: the largest weight in [2^13, 2^14)
+    s = 2.0 ** (14 - np.frexp(np.abs(w).max())[1])          # weight_pack.cpp x3_weight_scale: the largest weight in [2^13, 2^14)
     ws = w * s
     wh = f16(ws)
     wl = ws - wh
