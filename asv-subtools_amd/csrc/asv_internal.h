@@ -358,6 +358,36 @@ struct ConvTapsParams {
 };
 int launch_grid_conv_taps(const ConvTapsParams &p, int et, hipStream_t s);
 
+// the transformer encoder's kernels (kernels_attention.hip)
+constexpr int kAttentionMaxDk = 128;         // head width: a multiple of 16 up to this (four 32-column accumulator tiles per wave)
+struct AttentionKernelParams {
+  const void *q, *k, *v; void *out;          // already offset to their channel views: heads * d_k columns each, head h at column h * d_k
+  int ldq, ldk, ldv, ldo;
+  int heads, d_k;
+  float scale;                               // 1 / sqrt(d_k), applied to the f32 scores
+  const int32_t *seg_row0, *seg_len;         // the sequence's segments: softmax over the rows of the same segment only
+  int segments, max_len;                     // max_len: the longest segment of the batch in rows (sizes the grid)
+  int rows;                                  // padded row count of the domain: the gap rows up to it are written as zeros
+};
+int launch_self_attention(const AttentionKernelParams &p, int et, hipStream_t s);
+// y = x * scale + pe[row - first row of the segment]; gap rows and pad columns become zeros
+struct PosencKernelParams {
+  const void *in; void *out; int ldi, ldo, channels, rows;
+  float scale;
+  const float *pe; int ld_pe;                // [positions][ld_pe], zeros behind the channels
+  const int32_t *row_seg, *seg_row0; const uint32_t *row_valid;
+};
+int launch_posenc(const PosencKernelParams &p, int et, hipStream_t s);
+// first stage of the unpadded stride-2 front: feature rows [t][f] -> grid rows (t', f') of `channels` channels,
+// out = relu(bias + sum_{i, j < 3} w[c][3 i + j] x[2 t' + i][2 f' + j])
+struct FrontConvParams {
+  const void *x; int ldx;                    // the frames-domain feature rows
+  void *out; int ldo, channels, rows, pitch; // the whole grid buffer (pad channels are zeroed)
+  const float *w, *bias;                     // [channels][9] (time-major taps), [channels]
+  const int32_t *fr_row0, *g_row0, *row_seg; const uint32_t *row_valid;
+};
+int launch_front_conv(const FrontConvParams &p, int et, hipStream_t s);
+
 // float64 score matrices of the PLDA back-end (kernels_score_matrix.hip): C[i][j] = sum_k A[i][k] B[j][k] + row[i] + col[j] on the f64
 // matrix instruction.  A [m][kp], B [n][kp] float64 with kp a multiple of kScoreMatrixKChunk and zeros beyond the real K (the
 // preparation kernels write them), row [m], col [n] or nullptr, C dense [m][n] float (the LLR) or double (two-covariance).

@@ -44,12 +44,13 @@ struct Domain {
   int kind;                // ASV_DOMAIN_FRAMES / ASV_DOMAIN_UTTS / 2 (grid)
   int shift = 0, width = 1, pitch = 1;
   int reach = 1;           // grids: 2 = pitch >= width + 2 and gaps that cover +-(2 pitch + 2) rows (asv_net_define_grid_reach)
+  bool valid = false;      // grids: a segment owns L(T) frames, L the chain n -> (n - 1) / 2 per shift (asv_net_define_grid_valid); else ceil(T / 2^shift)
   int halo() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : (kind == ASV_DOMAIN_UTTS ? 0 : pitch + 1); }      // what a TDNN layer may reach
   int conv_halo() const { return kind == 2 ? reach * pitch + reach : 0; }                                          // what asv_net_add_grid_conv may reach
   int gap() const { return kind == ASV_DOMAIN_FRAMES ? kHalo : (reach == 2 ? 2 * pitch + 3 : pitch + 2); }
 };
 
-enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10, OP_ROWOP = 11, OP_GRID_CONV = 12 };
+enum OpKind { OP_TDNN = 0, OP_POOL = 1, OP_ATTPOOL = 2, OP_ELTWISE = 3, OP_GRID_INPUT = 4, OP_IM2COL = 5, OP_LDE = 6, OP_RES2 = 7, OP_FLATTEN = 8, OP_MQ_ATTPOOL = 9, OP_RES2N = 10, OP_ROWOP = 11, OP_GRID_CONV = 12, OP_ATTENTION = 13, OP_POSENC = 14, OP_FRONT_CONV = 15 };
 
 struct Op {
   OpKind kind;
@@ -67,6 +68,9 @@ struct Op {
   asv_res2_desc_t res2;          // fragments in `wfrag`, per-branch constants in bias / scale / shift
   asv_rowop_desc_t rop;          // host pointers nulled; the per-channel tables live in `rop_tab`
   asv_grid_conv_desc_t gconv;    // host pointers nulled; fragments of pack_grid_conv_taps in `wconv`, bias in `bias`
+  asv_self_attention_desc_t sa;
+  asv_posenc_desc_t pos;         // host pointer nulled; the table [pe_rows][round_up(channels, 16)] in `scale`
+  asv_front_conv_desc_t front;   // host pointers nulled; [out_ch][9] in `scale`, the bias in `bias`
   // device parameters
   void *w = nullptr;
   void *wfrag = nullptr;         // fragment-ordered copy for the variant-3 kernel (bf16 frame layers); pooled layers: bf16 hi halves
@@ -99,8 +103,8 @@ struct DevMem {
   size_t cap = 0;
 };
 
-const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain", "rowop", "grid_conv_taps"};
-enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_ROWOP, K_CONV_TAPS, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
+const char *kKernelNames[] = {"tdnn_gemm", "stats_pool", "attentive_pool", "eltwise", "rowmap", "pack_input", "combine", "grid_gather", "utts_gemm", "res2n_chain", "rowop", "grid_conv_taps", "self_attention", "posenc", "front_conv"};
+enum { K_TDNN = 0, K_POOL, K_ATT, K_ELT, K_ROWMAP, K_PACK, K_COMBINE, K_GATHER, K_UTTS, K_RES2N, K_ROWOP, K_CONV_TAPS, K_ATTENTION, K_POSENC, K_FRONT_CONV, K_COUNT };   // K_UTTS: affine layers of the pooled domain; K_RES2N: res2n_chain_kernel (its own row: tools/res2n_profile_workload.py)
 
 }  // namespace
 }  // namespace asv
@@ -157,7 +161,7 @@ struct asv_net {
 
 namespace {
 
-std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_CONV_TAPS + 1];       // asv_kernel_launch_count (ids start at 1)
+std::atomic<unsigned long long> g_kernel_launches[ASV_KERNEL_FRONT_CONV + 1];       // asv_kernel_launch_count (ids start at 1)
 
 // the range-status word of the f32x kernels lives behind the zero page's zeros (own 64-byte line; kernels only ever OR into it)
 uint32_t *status_word(asv_net *net) { return reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(net->zero_page) + 128); }
@@ -363,7 +367,9 @@ int make_plan(const asv_net *net, const int32_t *offsets, int n_utts, int max_ch
     dp.seg_row0.reserve(bp.segments); dp.seg_len.reserve(bp.segments);
     for (int sidx = 0; sidx < bp.segments; ++sidx) {
       long long fr = bp.seg_frames[sidx];
-      for (int k = 0; k < dm.shift; ++k) fr = (fr + 1) / 2;       // stride-2 stages: ceil(T/2) each
+      for (int k = 0; k < dm.shift; ++k) fr = dm.valid ? (fr - 1) / 2 : (fr + 1) / 2;       // stride-2 stages: ceil(T/2) each; unpadded ones: (T - 1) / 2
+      ASV_REQUIRE(fr >= 1, "extract: a chunk of %d frames is too short for the unpadded subsampling front (%d stride-2 stages of kernel 3: at least %d frames)",
+                  (int)bp.seg_frames[sidx], dm.shift, (1 << (dm.shift + 1)) - 1);
       const long long len = fr * dm.pitch;
       dp.seg_row0.push_back((int32_t)row);
       dp.seg_len.push_back((int32_t)len);
@@ -456,6 +462,13 @@ int asv_net_define_grid_reach(asv_net_t *net, int time_shift, int width, int pit
   d.shift = time_shift; d.width = width; d.pitch = pitch; d.reach = 2;
   net->domains.push_back(d);
   return (int)net->domains.size() - 1;
+}
+
+int asv_net_define_grid_valid(asv_net_t *net, int time_shift, int width, int pitch) {
+  ASV_REQUIRE(time_shift >= 1, "asv_net_define_grid_valid: time_shift %d (at least one unpadded stride-2 stage)", time_shift);
+  const int id = asv_net_define_grid(net, time_shift, width, pitch);
+  if (id >= 0) net->domains[id].valid = true;
+  return id;
 }
 
 int asv_net_new_buffer(asv_net_t *net, int domain, int channels) {
@@ -826,8 +839,18 @@ int asv_net_add_im2col(asv_net_t *net, const asv_im2col_desc_t *d) {
   if ((rc = check_view(net, d->out_buf, 0, d->channels * d->n_taps, "im2col output"))) return rc;
   const Domain &di = net->domains[net->bufs[d->in_buf].domain], &dq = net->domains[net->bufs[d->out_buf].domain];
   ASV_REQUIRE(di.kind == 2 && dq.kind == 2 && d->out_buf != d->in_buf && d->out_buf != 0, "im2col: grid -> grid");
-  ASV_REQUIRE(dq.shift == di.shift + (d->stride == 2 ? 1 : 0) && dq.width == (di.width + d->stride - 1) / d->stride,
-              "im2col: output grid (T/%d x %d) does not match stride %d over input grid (T/%d x %d)", 1 << dq.shift, dq.width, d->stride, 1 << di.shift, di.width);
+  if (dq.valid) {
+    // the unpadded stride-2 form: taps (0 .. 2, 0 .. 2) relative to (2 t', 2 f'), every one inside the input map by the domain rule
+    ASV_REQUIRE(di.valid && d->stride == 2 && dq.shift == di.shift + 1 && dq.width == (di.width - 1) / 2,
+                "im2col: unpadded output grid (shift %d, width %d) does not match stride 2 over the unpadded input grid (shift %d, width %d): width (W - 1) / 2", dq.shift, dq.width,
+                di.shift, di.width);
+    for (int t = 0; t < d->n_taps; ++t)
+      ASV_REQUIRE(d->dt[t] >= 0 && d->dt[t] <= 2 && d->df[t] >= 0 && d->df[t] <= 2, "im2col: tap (%d, %d) of the unpadded form (0 .. 2 in both axes)", d->dt[t], d->df[t]);
+  } else {
+    ASV_REQUIRE(!di.valid, "im2col: a padded gather from an unpadded grid");
+    ASV_REQUIRE(dq.shift == di.shift + (d->stride == 2 ? 1 : 0) && dq.width == (di.width + d->stride - 1) / d->stride,
+                "im2col: output grid (T/%d x %d) does not match stride %d over input grid (T/%d x %d)", 1 << dq.shift, dq.width, d->stride, 1 << di.shift, di.width);
+  }
   ASV_REQUIRE(d->act == ASV_ACT_NONE || d->act == ASV_ACT_RELU, "im2col: the elementwise prologue takes no activation or ReLU (got %d)", d->act);
   // optional buffers: -1 = none, and so is 0 - buffer 0 is the feature matrix (frames domain), which can be neither a grid addend nor a
   // per-segment scale, so a caller that zero-initialises the descriptor (memset + struct_size, the usual C pattern) gets what the
@@ -855,11 +878,88 @@ int asv_net_add_grid_flatten(asv_net_t *net, const asv_grid_flatten_desc_t *d) {
   ASV_REQUIRE(d->in_buf > 0 && d->in_buf < (int)net->bufs.size() && d->out_buf > 0 && d->out_buf < (int)net->bufs.size() && d->in_buf != d->out_buf,
               "grid_flatten: buffer ids %d -> %d", d->in_buf, d->out_buf);
   const Domain &di = net->domains[net->bufs[d->in_buf].domain], &dq = net->domains[net->bufs[d->out_buf].domain];
-  ASV_REQUIRE(di.kind == 2 && dq.kind == 2 && dq.width == 1 && dq.pitch == 1 && dq.shift == di.shift,
-              "grid_flatten: the output must live on the sequence domain (width 1, pitch 1) of the input grid's time shift");
+  ASV_REQUIRE(di.kind == 2 && dq.kind == 2 && dq.width == 1 && dq.pitch == 1 && dq.shift == di.shift && dq.valid == di.valid,
+              "grid_flatten: the output must live on the sequence domain (width 1, pitch 1) of the input grid's time shift and row rule");
   ASV_REQUIRE(net->bufs[d->out_buf].channels == net->bufs[d->in_buf].channels * di.width, "grid_flatten: %d channels x %d bins do not give %d output channels",
               net->bufs[d->in_buf].channels, di.width, net->bufs[d->out_buf].channels);
   Op op; op.kind = OP_FLATTEN; op.flat = *d;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
+int asv_net_add_front_conv(asv_net_t *net, const asv_front_conv_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_front_conv: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_front_conv_desc_t), "asv_net_add_front_conv: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(asv_front_conv_desc_t));
+  ASV_REQUIRE(d->in_buf >= 0 && d->in_buf < (int)net->bufs.size() && net->bufs[d->in_buf].domain == ASV_DOMAIN_FRAMES && net->bufs[d->in_buf].channels == net->feat_dim,
+              "front_conv: the input must be a frames-domain buffer with feat_dim channels");
+  ASV_REQUIRE(d->out_buf > 0 && d->out_buf < (int)net->bufs.size() && d->out_buf != d->in_buf, "front_conv: output buffer id %d", d->out_buf);
+  ASV_REQUIRE(d->out_ch >= 1 && d->out_ch == net->bufs[d->out_buf].channels, "front_conv: out_ch %d must be the whole output buffer (%d channels)", d->out_ch,
+              net->bufs[d->out_buf].channels);
+  const Domain &dm = net->domains[net->bufs[d->out_buf].domain];
+  ASV_REQUIRE(dm.kind == 2 && dm.valid && dm.shift == 1 && dm.width == (net->feat_dim - 1) / 2 && dm.width >= 1 && dm.pitch > dm.width,
+              "front_conv: the output must live on the unpadded grid of time shift 1 and width (feat_dim - 1) / 2 = %d (asv_net_define_grid_valid)", (net->feat_dim - 1) / 2);
+  ASV_REQUIRE(d->weight != nullptr && d->bias != nullptr, "front_conv: null weight or bias");
+  Op op; op.kind = OP_FRONT_CONV; op.front = *d;
+  ASV_ON_DEVICE(net->device);
+  int rc;
+  if ((rc = upload_padded(net, d->weight, d->out_ch * 9, round_up(d->out_ch, kChanAlign) * 9, 0.0f, &op.scale))) return rc;
+  if ((rc = upload_padded(net, d->bias, d->out_ch, round_up(d->out_ch, kChanAlign), 0.0f, &op.bias))) return rc;
+  op.front.weight = nullptr; op.front.bias = nullptr;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
+int asv_net_add_posenc(asv_net_t *net, const asv_posenc_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_posenc: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_posenc_desc_t), "asv_net_add_posenc: struct_size %u != %zu (ABI mismatch)", d->struct_size, sizeof(asv_posenc_desc_t));
+  int rc;
+  if ((rc = check_view(net, d->in_buf, d->in_ch_off, d->channels, "posenc input"))) return rc;
+  if ((rc = check_view(net, d->out_buf, d->out_ch_off, d->channels, "posenc output"))) return rc;
+  const int dom = net->bufs[d->in_buf].domain;
+  ASV_REQUIRE(net->is_sequence(dom), "posenc: frames and sequence domains only (one row per position)");
+  ASV_REQUIRE(net->bufs[d->out_buf].domain == dom && d->out_buf != 0, "posenc: bad output buffer (the input's domain, never the feature buffer)");
+  const int vec = net->dom_et(dom) != ET_F32 ? 8 : 4;
+  ASV_REQUIRE(d->in_ch_off + round_up(d->channels, vec) <= net->bufs[d->in_buf].ld && d->out_ch_off + round_up(d->channels, vec) <= net->bufs[d->out_buf].ld,
+              "posenc: padded view exceeds pitch");
+  ASV_REQUIRE(d->in_buf != d->out_buf || d->in_ch_off == d->out_ch_off || d->in_ch_off + round_up(d->channels, kChanAlign) <= d->out_ch_off ||
+              d->out_ch_off + round_up(d->channels, kChanAlign) <= d->in_ch_off, "posenc: the output view overlaps the input view without being it (in place: the same offset)");
+  ASV_REQUIRE(d->pe != nullptr && d->pe_rows >= 1 && d->pe_rows <= (1 << 20), "posenc: null table or pe_rows %d", d->pe_rows);
+  ASV_REQUIRE(std::isfinite(d->scale), "posenc: scale %g", (double)d->scale);
+  Op op; op.kind = OP_POSENC; op.pos = *d;
+  ASV_ON_DEVICE(net->device);
+  const int ld = round_up(d->channels, kChanAlign);
+  std::vector<float> tab((size_t)d->pe_rows * ld, 0.0f);
+  for (int r = 0; r < d->pe_rows; ++r) memcpy(&tab[(size_t)r * ld], d->pe + (size_t)r * d->channels, (size_t)d->channels * sizeof(float));
+  void *dev = nullptr;
+  if ((rc = upload_vec(net, tab, &dev))) return rc;
+  op.scale = reinterpret_cast<float *>(dev);
+  op.pos.pe = nullptr;
+  net->ops.push_back(op);
+  return ASV_OK;
+}
+
+int asv_net_add_self_attention(asv_net_t *net, const asv_self_attention_desc_t *d) {
+  ASV_REQUIRE(net && d && !net->finalized, "asv_net_add_self_attention: net is null or finalized");
+  ASV_REQUIRE(d->struct_size == sizeof(asv_self_attention_desc_t), "asv_net_add_self_attention: struct_size %u != %zu (ABI mismatch)", d->struct_size,
+              sizeof(asv_self_attention_desc_t));
+  ASV_REQUIRE(d->heads >= 1 && d->heads <= 4096, "self_attention: %d heads (1 .. 4096)", d->heads);
+  ASV_REQUIRE(d->d_k >= 16 && d->d_k <= kAttentionMaxDk && d->d_k % 16 == 0, "self_attention: d_k %d (a multiple of 16 up to %d)", d->d_k, kAttentionMaxDk);
+  const int ch = d->heads * d->d_k;
+  int rc;
+  if ((rc = check_view(net, d->q_buf, d->q_ch_off, ch, "self_attention q"))) return rc;
+  if ((rc = check_view(net, d->k_buf, d->k_ch_off, ch, "self_attention k"))) return rc;
+  if ((rc = check_view(net, d->v_buf, d->v_ch_off, ch, "self_attention v"))) return rc;
+  if ((rc = check_view(net, d->out_buf, d->out_ch_off, ch, "self_attention out"))) return rc;
+  const int dom = net->bufs[d->q_buf].domain;
+  ASV_REQUIRE(net->is_sequence(dom), "self_attention: frames and sequence domains only (one row per position)");
+  ASV_REQUIRE(net->bufs[d->k_buf].domain == dom && net->bufs[d->v_buf].domain == dom && net->bufs[d->out_buf].domain == dom && d->out_buf != 0,
+              "self_attention: q, k, v and out must share one domain, and out is never the feature buffer");
+  // other workgroups read the key / value rows (and the queries of other heads) while this one stores its output rows
+  const int in_bufs[3] = {d->q_buf, d->k_buf, d->v_buf}, in_offs[3] = {d->q_ch_off, d->k_ch_off, d->v_ch_off};
+  for (int i = 0; i < 3; ++i)
+    ASV_REQUIRE(in_bufs[i] != d->out_buf || in_offs[i] + ch <= d->out_ch_off || d->out_ch_off + ch <= in_offs[i], "self_attention: the out view overlaps the %s view",
+                i == 0 ? "q" : (i == 1 ? "k" : "v"));
+  Op op; op.kind = OP_ATTENTION; op.sa = *d;
   net->ops.push_back(op);
   return ASV_OK;
 }
@@ -888,7 +988,9 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                              o.kind == OP_POOL ? o.pool.in_buf : -1, o.kind == OP_ATTPOOL ? o.att.x_buf : -1, o.kind == OP_ATTPOOL ? o.att.logit_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.x_buf : -1, o.kind == OP_MQ_ATTPOOL ? o.mq.logit_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                              o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
-                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1, o.kind == OP_GRID_CONV ? o.gconv.in_buf : -1};
+                             o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1, o.kind == OP_GRID_CONV ? o.gconv.in_buf : -1,
+                             o.kind == OP_ATTENTION ? o.sa.q_buf : -1, o.kind == OP_ATTENTION ? o.sa.k_buf : -1, o.kind == OP_ATTENTION ? o.sa.v_buf : -1,
+                             o.kind == OP_POSENC ? o.pos.in_buf : -1, o.kind == OP_FRONT_CONV ? o.front.in_buf : -1};
         for (int rbuf : reads) other_reader |= (rbuf == d.out_buf);
       }
       if (other_reader || d.out_buf == out_buf) continue;
@@ -907,7 +1009,9 @@ int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim) {
                            o.kind == OP_ELTWISE ? o.elt.a_buf : -1, o.kind == OP_ELTWISE ? o.elt.b_buf : -1, o.kind == OP_ELTWISE ? o.elt.c_buf : -1,
                            o.kind == OP_ELTWISE ? o.elt.seg_scale_buf : -1, o.kind == OP_ELTWISE ? o.elt.seg_norm_buf : -1, o.kind == OP_ELTWISE ? o.elt.d_buf : -1,
                            o.kind == OP_IM2COL ? o.i2c.in_buf : -1, o.kind == OP_IM2COL ? o.i2c.b_buf : -1, o.kind == OP_IM2COL ? o.i2c.seg_scale_buf : -1, o.kind == OP_LDE ? o.lde.x_buf : -1, o.kind == OP_GRID_INPUT ? o.gin.in_buf : -1,
-                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1, o.kind == OP_GRID_CONV ? o.gconv.in_buf : -1};
+                           o.kind == OP_RES2 ? o.res2.in_buf : -1, o.kind == OP_RES2N ? o.res2n.in_buf : -1, o.kind == OP_FLATTEN ? o.flat.in_buf : -1, o.kind == OP_ROWOP ? o.rop.in_buf : -1, o.kind == OP_GRID_CONV ? o.gconv.in_buf : -1,
+                             o.kind == OP_ATTENTION ? o.sa.q_buf : -1, o.kind == OP_ATTENTION ? o.sa.k_buf : -1, o.kind == OP_ATTENTION ? o.sa.v_buf : -1,
+                             o.kind == OP_POSENC ? o.pos.in_buf : -1, o.kind == OP_FRONT_CONV ? o.front.in_buf : -1};
       for (int rbuf : reads) if (rbuf == buf) return false;
     }
     return true;
@@ -1026,7 +1130,7 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream) {
 }
 
 unsigned long long asv_kernel_launch_count(int which) {
-  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_CONV_TAPS) ? g_kernel_launches[which].load() : 0ull;
+  return (which >= ASV_KERNEL_TDNN_P8 && which <= ASV_KERNEL_FRONT_CONV) ? g_kernel_launches[which].load() : 0ull;
 }
 
 size_t asv_net_device_bytes(const asv_net_t *net) {
@@ -1047,6 +1151,7 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
     const Domain &dm = net->domains[net->bufs[i].domain];
     char dname[64];
     if (dm.kind == 2 && dm.reach == 2) snprintf(dname, sizeof(dname), "grid(T/%d x %d, pitch %d, reach 2)", 1 << dm.shift, dm.width, dm.pitch);
+    else if (dm.kind == 2 && dm.valid) snprintf(dname, sizeof(dname), "grid(%d unpadded stride-2 stages x %d, pitch %d)", dm.shift, dm.width, dm.pitch);
     else if (dm.kind == 2) snprintf(dname, sizeof(dname), "grid(T/%d x %d, pitch %d)", 1 << dm.shift, dm.width, dm.pitch);
     else snprintf(dname, sizeof(dname), "%s", dm.kind == ASV_DOMAIN_FRAMES ? "frames" : "utts");
     snprintf(line, sizeof(line), "  buf %zu: %s channels=%d ld=%d\n", i, dname, net->bufs[i].channels, net->bufs[i].ld);
@@ -1109,6 +1214,17 @@ int asv_net_describe(const asv_net_t *net, char *buf, size_t cap) {
       case OP_GRID_CONV:
         snprintf(line, sizeof(line), "  op %zu: grid_conv %d[%d:+%d] -> %d[%d:+%d] taps=%d act=%d bias=%d\n", i, op.gconv.in_buf, op.gconv.in_ch_off, op.gconv.in_ch,
                  op.gconv.out_buf, op.gconv.out_ch_off, op.gconv.out_ch, op.gconv.n_taps, op.gconv.act, op.bias != nullptr);
+        break;
+      case OP_ATTENTION:
+        snprintf(line, sizeof(line), "  op %zu: self_attention q=%d[%d] k=%d[%d] v=%d[%d] heads=%d d_k=%d -> %d[%d]\n", i, op.sa.q_buf, op.sa.q_ch_off, op.sa.k_buf, op.sa.k_ch_off,
+                 op.sa.v_buf, op.sa.v_ch_off, op.sa.heads, op.sa.d_k, op.sa.out_buf, op.sa.out_ch_off);
+        break;
+      case OP_POSENC:
+        snprintf(line, sizeof(line), "  op %zu: posenc %d[%d:+%d] -> %d[%d] scale=%g positions=%d\n", i, op.pos.in_buf, op.pos.in_ch_off, op.pos.channels, op.pos.out_buf,
+                 op.pos.out_ch_off, (double)op.pos.scale, op.pos.pe_rows);
+        break;
+      case OP_FRONT_CONV:
+        snprintf(line, sizeof(line), "  op %zu: front_conv %d -> %d channels=%d\n", i, op.front.in_buf, op.front.out_buf, op.front.out_ch);
         break;
     }
     s += line;
@@ -1807,6 +1923,68 @@ int run_ops(RunCtx &c, size_t n_ops) {
         if ((rc = prof.begin(K_CONV_TAPS, 2.0 * frames * d.in_ch * d.out_ch * d.n_taps, (int)i))) return rc;
         if ((rc = launch_grid_conv_taps(p, net->dom_et(domid), c.s))) return rc;
         ++g_kernel_launches[ASV_KERNEL_CONV_TAPS];
+        if ((rc = prof.end())) return rc;
+        break;
+      }
+      case OP_ATTENTION: {
+        const auto &d = op.sa;
+        const int domid = net->bufs[d.q_buf].domain;
+        const DomainRun &dr = c.dom[domid];
+        ASV_REQUIRE(!c.buf_image[d.q_buf] && !c.buf_image[d.k_buf] && !c.buf_image[d.v_buf], "self_attention: image rows reached the attention op (internal)");
+        AttentionKernelParams p;
+        memset(&p, 0, sizeof(p));
+        p.q = view(c, d.q_buf, d.q_ch_off); p.ldq = net->bufs[d.q_buf].ld;
+        p.k = view(c, d.k_buf, d.k_ch_off); p.ldk = net->bufs[d.k_buf].ld;
+        p.v = view(c, d.v_buf, d.v_ch_off); p.ldv = net->bufs[d.v_buf].ld;
+        p.out = view(c, d.out_buf, d.out_ch_off); p.ldo = net->bufs[d.out_buf].ld;
+        p.heads = d.heads; p.d_k = d.d_k; p.scale = 1.0f / std::sqrt((float)d.d_k);
+        p.seg_row0 = dr.seg_row0; p.seg_len = dr.seg_len; p.segments = bp.segments; p.rows = dr.rows_pad;
+        double pairs = 0;                             // (query, key) pairs of the batch
+        for (int32_t len : bp.dom[domid].seg_len) { p.max_len = std::max(p.max_len, (int)len); pairs += (double)len * len; }
+        if ((rc = prof.begin(K_ATTENTION, 4.0 * pairs * d.heads * d.d_k, (int)i))) return rc;
+        if ((rc = launch_self_attention(p, net->dom_et(domid), c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_ATTENTION];
+        if ((rc = prof.end())) return rc;
+        break;
+      }
+      case OP_POSENC: {
+        const auto &d = op.pos;
+        const int domid = net->bufs[d.in_buf].domain;
+        const DomainRun &dr = c.dom[domid];
+        ASV_REQUIRE(!c.buf_image[d.in_buf], "posenc: image rows reached the positional encoding (internal)");
+        for (int32_t len : bp.dom[domid].seg_len)
+          ASV_REQUIRE(len < d.pe_rows, "extract: a chunk of %d positions reaches the end of the positional-encoding table (%d rows; the reference asserts rows < max_len)", (int)len,
+                      d.pe_rows);
+        PosencKernelParams p;
+        memset(&p, 0, sizeof(p));
+        p.in = view(c, d.in_buf, d.in_ch_off); p.ldi = net->bufs[d.in_buf].ld;
+        p.out = view(c, d.out_buf, d.out_ch_off); p.ldo = net->bufs[d.out_buf].ld;
+        p.channels = d.channels; p.rows = dr.rows_pad; p.scale = d.scale;
+        p.pe = op.scale; p.ld_pe = round_up(d.channels, kChanAlign);
+        p.row_seg = dr.row_seg; p.seg_row0 = dr.seg_row0; p.row_valid = dr.row_valid;
+        if ((rc = prof.begin(K_POSENC, 0, (int)i))) return rc;
+        if ((rc = launch_posenc(p, net->dom_et(domid), c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_POSENC];
+        if ((rc = prof.end())) return rc;
+        break;
+      }
+      case OP_FRONT_CONV: {
+        const auto &d = op.front;
+        const int domid = net->bufs[d.out_buf].domain;
+        const Domain &dm = net->domains[domid];
+        const DomainRun &dg = c.dom[domid];
+        FrontConvParams p;
+        memset(&p, 0, sizeof(p));
+        p.x = net->arena[d.in_buf].ptr; p.ldx = net->bufs[d.in_buf].ld;
+        p.out = net->arena[d.out_buf].ptr; p.ldo = net->bufs[d.out_buf].ld;
+        p.channels = d.out_ch; p.rows = dg.rows_pad; p.pitch = dm.pitch;
+        p.w = op.scale; p.bias = op.bias;
+        p.fr_row0 = c.dom[ASV_DOMAIN_FRAMES].seg_row0; p.g_row0 = dg.seg_row0; p.row_seg = dg.row_seg; p.row_valid = dg.row_valid;
+        double positions = 0;
+        for (int32_t len : bp.dom[domid].seg_len) positions += (double)len / dm.pitch * dm.width;
+        if ((rc = prof.begin(K_FRONT_CONV, 2.0 * positions * 9 * d.out_ch, (int)i))) return rc;
+        if ((rc = launch_front_conv(p, net->frames_et(), c.s))) return rc;
+        ++g_kernel_launches[ASV_KERNEL_FRONT_CONV];
         if ((rc = prof.end())) return rc;
         break;
       }

@@ -27,6 +27,7 @@ KERNEL_CONV_C1, KERNEL_CONV_NARROW, KERNEL_CONV_NARROW_PERS, KERNEL_CONV_WIDE, K
 KERNEL_RES2N = 13
 KERNEL_ROWOP = 14
 KERNEL_CONV_TAPS = 15
+KERNEL_ATTENTION, KERNEL_POSENC, KERNEL_FRONT_CONV = 16, 17, 18      # kernels_attention.hip
 GRID_CONV_MAX_TAPS = 25
 RES2N_TILE_ROWS = 192          # ASV_RES2N_TILE_ROWS: rows a workgroup of res2n_chain_kernel produces
 
@@ -181,6 +182,29 @@ class GridConvDesc(C.Structure):
     ]
 
 
+class FrontConvDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("in_buf", C.c_int32), ("out_buf", C.c_int32), ("out_ch", C.c_int32), ("weight", c_float_p), ("bias", c_float_p)]
+
+
+class PosencDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("channels", C.c_int32),
+        ("in_buf", C.c_int32), ("in_ch_off", C.c_int32), ("out_buf", C.c_int32), ("out_ch_off", C.c_int32),
+        ("scale", C.c_float),
+        ("pe", c_float_p), ("pe_rows", C.c_int32),
+    ]
+
+
+class SelfAttentionDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("q_buf", C.c_int32), ("q_ch_off", C.c_int32), ("k_buf", C.c_int32), ("k_ch_off", C.c_int32), ("v_buf", C.c_int32), ("v_ch_off", C.c_int32),
+        ("heads", C.c_int32), ("d_k", C.c_int32),
+        ("out_buf", C.c_int32), ("out_ch_off", C.c_int32),
+    ]
+
+
 class FbankOpts(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -223,6 +247,7 @@ SYMBOLS = [
     "asv_fbank_num_frames", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
     "asv_ingest_frames", "asv_decode_compressed", "asv_ingest_windows", "asv_desilence_pcm16",
     "asv_net_define_grid_reach", "asv_net_add_grid_conv",
+    "asv_net_define_grid_valid", "asv_net_add_front_conv", "asv_net_add_posenc", "asv_net_add_self_attention",
 ]
 
 
@@ -258,6 +283,10 @@ def lib():
     L.asv_net_define_grid.argtypes = [vp, ci, ci, ci]
     L.asv_net_define_grid_reach.argtypes = [vp, ci, ci, ci, ci]
     L.asv_net_add_grid_conv.argtypes = [vp, C.POINTER(GridConvDesc)]
+    L.asv_net_define_grid_valid.argtypes = [vp, ci, ci, ci]
+    L.asv_net_add_front_conv.argtypes = [vp, C.POINTER(FrontConvDesc)]
+    L.asv_net_add_posenc.argtypes = [vp, C.POINTER(PosencDesc)]
+    L.asv_net_add_self_attention.argtypes = [vp, C.POINTER(SelfAttentionDesc)]
     L.asv_net_add_grid_input.argtypes = [vp, C.POINTER(GridInputDesc)]
     L.asv_net_add_im2col.argtypes = [vp, C.POINTER(Im2colDesc)]
     L.asv_net_add_grid_flatten.argtypes = [vp, C.POINTER(GridFlattenDesc)]

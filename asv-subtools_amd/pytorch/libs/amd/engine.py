@@ -138,6 +138,10 @@ class Engine(object):
                 dom_of[i] = capi.check(L.asv_net_define_grid(self._net, spec[1], spec[2], spec[3]), "asv_net_define_grid")
             elif spec[0] == "seq":                   # one row per frame at the grid's rate = a grid of width 1, pitch 1
                 dom_of[i] = capi.check(L.asv_net_define_grid(self._net, spec[1], 1, 1), "asv_net_define_grid")
+            elif spec[0] == "vgrid":                 # behind the unpadded stride-2 front (ir.Graph.valid_grid_domain)
+                dom_of[i] = capi.check(L.asv_net_define_grid_valid(self._net, spec[1], spec[2], spec[3]), "asv_net_define_grid_valid")
+            elif spec[0] == "vseq":
+                dom_of[i] = capi.check(L.asv_net_define_grid_valid(self._net, spec[1], 1, 1), "asv_net_define_grid_valid")
         for tid in written:
             dom, ch = g.tensors[tid]
             buf_of[tid] = capi.check(L.asv_net_new_buffer(self._net, dom_of[dom], ch), "asv_net_new_buffer")
@@ -274,6 +278,29 @@ class Engine(object):
                 d.act = capi.ACT_BY_NAME[op.act]
                 capi.check(L.asv_net_add_grid_conv(self._net, C.byref(d)), "asv_net_add_grid_conv")
                 del keep
+            elif op.kind == "front_conv":
+                d = capi.FrontConvDesc()
+                d.struct_size = C.sizeof(capi.FrontConvDesc)
+                d.in_buf, d.out_buf, d.out_ch = buf_of[op.inp.tid], buf_of[op.out.tid], op.out.channels
+                d.weight, d.bias = capi.f32_ptr(op.weight), capi.f32_ptr(op.bias)
+                capi.check(L.asv_net_add_front_conv(self._net, C.byref(d)), "asv_net_add_front_conv")
+            elif op.kind == "posenc":
+                d = capi.PosencDesc()
+                d.struct_size = C.sizeof(capi.PosencDesc)
+                d.channels = op.inp.channels
+                d.in_buf, d.in_ch_off = bv(op.inp)
+                d.out_buf, d.out_ch_off = bv(op.out)
+                d.scale, d.pe, d.pe_rows = op.scale, capi.f32_ptr(op.pe), op.pe.shape[0]
+                capi.check(L.asv_net_add_posenc(self._net, C.byref(d)), "asv_net_add_posenc")
+            elif op.kind == "self_attention":
+                d = capi.SelfAttentionDesc()
+                d.struct_size = C.sizeof(capi.SelfAttentionDesc)
+                d.q_buf, d.q_ch_off = bv(op.q)
+                d.k_buf, d.k_ch_off = bv(op.k)
+                d.v_buf, d.v_ch_off = bv(op.v)
+                d.heads, d.d_k = op.heads, op.d_k
+                d.out_buf, d.out_ch_off = bv(op.out)
+                capi.check(L.asv_net_add_self_attention(self._net, C.byref(d)), "asv_net_add_self_attention")
             elif op.kind == "grid_input":
                 d = capi.GridInputDesc()
                 d.struct_size = C.sizeof(capi.GridInputDesc)
@@ -354,6 +381,7 @@ class Engine(object):
         n = len(offsets) - 1
         assert feats.dim() == 2 and feats.shape[1] == self.feat_dim, "expected [frames, %d] features, got %s" % (self.feat_dim, tuple(feats.shape))
         assert int(offsets[-1]) == feats.shape[0], "offsets[-1]=%d but feats has %d rows" % (int(offsets[-1]), feats.shape[0])
+        self.check_chunk_lengths(offsets, max_chunk)
         if out is None:
             out = torch.empty((n, self.embed_dim), dtype=torch.float32, device=feats.device)
         if stream is None:
@@ -361,6 +389,21 @@ class Engine(object):
         capi.check(self.lib.asv_net_extract(self._net, C.c_void_p(feats.data_ptr()), offsets.ctypes.data_as(capi.c_int32_p), n,
                                             C.c_void_p(out.data_ptr()), int(max_chunk), C.c_void_p(stream)), "asv_net_extract")
         return out
+
+    def check_chunk_lengths(self, offsets, max_chunk):
+        """ValueError - before any launch - when a chunk of the batch is too short to own a row behind the program's unpadded
+        subsampling front (Conv2dSubsampling4: fewer than 7 frames; the reference fails inside its second convolution).  The chunks
+        are the library's: ceil(T / max_chunk) near-equal pieces, the last one taking the remainder."""
+        need = self.graph.min_frames()
+        if need <= 1:
+            return
+        lens = np.diff(np.asarray(offsets, dtype=np.int64))
+        mc = int(max_chunk) if int(max_chunk) > 0 else 10000
+        shortest = lens // np.maximum(-(-lens // mc), 1)          # every chunk but the last has T // num_split frames, the last at least as many
+        if lens.size and int(shortest.min()) < need:
+            u = int(np.argmin(shortest))
+            raise ValueError("utterance %d: %d frames in chunks of at most %d give a chunk of %d frames; the unpadded subsampling front needs at "
+                             "least %d" % (u, int(lens[u]), mc, int(shortest[u]), need))
 
     def extract_device_guarded(self, feats, offsets, max_chunk=10000, out=None):
         """extract_device() + the range guard of extract_batch(), for synchronous callers that hold their batch on the device

@@ -48,7 +48,7 @@ class View(object):
 
 
 class Op(object):
-    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','rowop','cat','grid_input','im2col','grid_conv'}; `out` is a View covering
+    """kind in {'tdnn','pool','attpool','mqattpool','eltwise','rowop','cat','grid_input','im2col','grid_conv','front_conv','posenc','self_attention'}; `out` is a View covering
     a whole tensor until concat elision redirects it into a slice of a wider one."""
 
     def __init__(self, kind, out, **attrs):
@@ -68,8 +68,10 @@ class Op(object):
             names = ("a", "b", "c", "seg_scale", "seg_norm", "d")
         elif self.kind == "im2col":
             names = ("inp", "b", "seg_scale")
-        elif self.kind in ("grid_input", "res2", "res2n", "flatten", "rowop", "grid_conv"):
+        elif self.kind in ("grid_input", "res2", "res2n", "flatten", "rowop", "grid_conv", "front_conv", "posenc"):
             names = ("inp",)
+        elif self.kind == "self_attention":
+            names = ("q", "k", "v")
         else:
             return list(self.parts)
         return [getattr(self, n) for n in names if getattr(self, n, None) is not None]
@@ -77,7 +79,8 @@ class Op(object):
     def input_names(self):
         return {"tdnn": ("inp", "inp2", "seg_bias", "seg_scale", "res"), "pool": ("inp",),
                 "attpool": ("x", "logits"), "mqattpool": ("x", "logits"), "lde": ("x",), "eltwise": ("a", "b", "c", "seg_scale", "seg_norm", "d"), "cat": (), "grid_input": ("inp",),
-                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",), "rowop": ("inp",), "grid_conv": ("inp",)}[self.kind]
+                "im2col": ("inp", "b", "seg_scale"), "res2": ("inp",), "res2n": ("inp",), "flatten": ("inp",), "rowop": ("inp",), "grid_conv": ("inp",),
+                "front_conv": ("inp",), "posenc": ("inp",), "self_attention": ("q", "k", "v")}[self.kind]
 
 
 class Graph(object):
@@ -87,7 +90,9 @@ class Graph(object):
         self.feat_dim = int(feat_dim)
         # row domains: 0 frames, 1 utts, >= 2 (time, frequency) grids ("grid", time_shift, width, pitch) - reach-2 grids
         # ("grid", time_shift, width, pitch, 2): pitch >= width + 2 and wider gaps, for the 5 x 5 kernels of RepSPK - and the sequences
-        # ("seq", time_shift) their flattened [B, C*F, T'] views live on (one row per frame of the subsampled time axis)
+        # ("seq", time_shift) their flattened [B, C*F, T'] views live on (one row per frame of the subsampled time axis).  The unpadded
+        # stride-2 front of the transformer encoders has its own: ("vgrid", stages, width, pitch) and ("vseq", stages), on which a segment of
+        # T frames owns L(T) frames, L the chain n -> (n - 1) // 2 per stage, where the others own ceil(T / 2^shift) (valid_frames)
         self.domains = [("frames",), ("utts",)]
         self.new_tensor(DOMAIN_FRAMES, feat_dim)        # tensor 0 = input features
         self.output = None                                # View (utts domain)
@@ -122,16 +127,42 @@ class Graph(object):
             self.domains.append(spec)
         return self.domains.index(spec)
 
+    def valid_grid_domain(self, stages, width):
+        """The (time, frequency) grid behind `stages` unpadded stride-2 stages of kernel 3, `width` bins wide (pitch = width + 1)."""
+        spec = ("vgrid", int(stages), int(width), int(width) + 1)
+        if width < 1 or spec[3] + 1 > 84:
+            raise TraceError("unpadded subsampling front: %d frequency bins behind %d stages (1 .. 82)" % (width, stages))
+        if spec not in self.domains:
+            self.domains.append(spec)
+        return self.domains.index(spec)
+
+    def valid_seq_domain(self, stages):
+        spec = ("vseq", int(stages))
+        if spec not in self.domains:
+            self.domains.append(spec)
+        return self.domains.index(spec)
+
     def seq_spec(self, tid):
         d = self.domains[self.domain(tid)]
-        return d if d[0] == "seq" else None
+        return d if d[0] in ("seq", "vseq") else None
+
+    def is_valid_domain(self, tid):
+        return self.domains[self.domain(tid)][0] in ("vgrid", "vseq")
+
+    def min_frames(self):
+        """The fewest frames a chunk needs to own a row in every domain of the program (1 without an unpadded front: 7 behind two stages)."""
+        need = 1
+        for d in self.domains:
+            if d[0] in ("vgrid", "vseq"):
+                need = max(need, (1 << (d[1] + 1)) - 1)
+        return need
 
     def is_utts(self, tid):
         return self.domains[self.domain(tid)][0] == "utts"
 
     def grid_spec(self, tid):
         d = self.domains[self.domain(tid)]
-        return d if d[0] == "grid" else None
+        return d if d[0] in ("grid", "vgrid") else None
 
     def grid_reach(self, tid):
         d = self.grid_spec(tid)
@@ -144,7 +175,7 @@ class Graph(object):
         assert weight.ndim == 3 and weight.shape[1] == inp.channels, (weight.shape, inp)
         taps = [int(t) for t in taps]
         dom = self.domain(inp.tid)
-        halo = MAX_HALO if dom == DOMAIN_FRAMES else (self.domains[dom][3] + 1 if self.domains[dom][0] == "grid" else (2 if self.domains[dom][0] == "seq" else 0))
+        halo = MAX_HALO if dom == DOMAIN_FRAMES else (self.domains[dom][3] + 1 if self.domains[dom][0] in ("grid", "vgrid") else (2 if self.domains[dom][0] in ("seq", "vseq") else 0))
         if max(abs(t) for t in taps) > halo and dom != DOMAIN_UTTS:
             raise TraceError("TDNN context %s reaches beyond the +-%d row halo of the MI355X row layout" % (taps, halo))
         if dom == DOMAIN_UTTS and taps != [0]:
@@ -173,13 +204,21 @@ class Graph(object):
         self.ops.append(Op("grid_input", out, inp=inp))
         return out
 
-    def im2col(self, inp, taps, stride):
-        """taps: [(dt, df)]; output grid = input grid subsampled by `stride` in both axes."""
+    def im2col(self, inp, taps, stride, valid=False):
+        """taps: [(dt, df)]; output grid = input grid subsampled by `stride` in both axes.  `valid`: the unpadded stride-2 form - taps
+        (0 .. 2, 0 .. 2) relative to (2 t', 2 f') of an unpadded grid, output width (W - 1) // 2, one more stage of the row rule."""
         g = self.grid_spec(inp.tid)
         assert g is not None and inp.ch_off == 0 and inp.channels == self.tensors[inp.tid][1]
         if inp.channels % CHAN_ALIGN != 0:
             raise TraceError("strided 2-D convolution over %d channels: the gather needs a multiple of %d" % (inp.channels, CHAN_ALIGN))
-        dom = self.grid_domain(g[1] + (1 if stride == 2 else 0), (g[2] + stride - 1) // stride, reach=self.grid_reach(inp.tid))
+        if valid:
+            if g[0] != "vgrid" or stride != 2 or any(not (0 <= a <= 2 and 0 <= b <= 2) for a, b in taps):
+                raise TraceError("im2col(valid=True): stride 2 over an unpadded grid with taps in 0 .. 2 (got stride %r, taps %r)" % (stride, taps))
+            dom = self.valid_grid_domain(g[1] + 1, (g[2] - 1) // 2)
+        elif g[0] == "vgrid":
+            raise TraceError("a padded gather from an unpadded grid")
+        else:
+            dom = self.grid_domain(g[1] + (1 if stride == 2 else 0), (g[2] + stride - 1) // stride, reach=self.grid_reach(inp.tid))
         out = self.full_view(self.new_tensor(dom, inp.channels * len(taps)))
         self.ops.append(Op("im2col", out, inp=inp, taps=[(int(a), int(b)) for a, b in taps], stride=int(stride)))
         return out
@@ -208,8 +247,50 @@ class Graph(object):
         sequence domain of the grid's time shift: what the frame-weighting poolings and frame-level layers behind the 2-D trunk read."""
         g = self.grid_spec(inp.tid)
         assert g is not None and inp.ch_off == 0 and inp.channels == self.tensors[inp.tid][1]
-        out = self.full_view(self.new_tensor(self.seq_domain(g[1]), inp.channels * g[2]))
+        out = self.full_view(self.new_tensor(self.valid_seq_domain(g[1]) if g[0] == "vgrid" else self.seq_domain(g[1]), inp.channels * g[2]))
         self.ops.append(Op("flatten", out, inp=inp))
+        return out
+
+    def front_conv(self, weight, bias, inp=None):
+        """First stage of the unpadded stride-2 front (asv_front_conv_desc_t): the features [T][F] as a one-channel image ->
+        relu(Conv2d(1, C, 3, stride 2, no padding)) on the unpadded grid of one stage, (F - 1) // 2 bins.  weight [C, 9] (index 3 i + j:
+        time offset i, frequency offset j), bias [C]."""
+        inp = inp or self.full_view(0)
+        weight = np.ascontiguousarray(weight, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+        if inp.channels != self.feat_dim or inp.ch_off != 0 or self.domain(inp.tid) != DOMAIN_FRAMES:
+            raise TraceError("front_conv reads the whole feature matrix")
+        if weight.ndim != 2 or weight.shape[1] != 9 or bias.shape[0] != weight.shape[0] or weight.shape[0] % CHAN_ALIGN != 0:
+            raise TraceError("front_conv: weight %s / bias %s ([C, 9] and [C], C a multiple of %d)" % (weight.shape, bias.shape, CHAN_ALIGN))
+        out = self.full_view(self.new_tensor(self.valid_grid_domain(1, (self.feat_dim - 1) // 2), weight.shape[0]))
+        self.ops.append(Op("front_conv", out, inp=inp, weight=weight, bias=bias))
+        return out
+
+    def posenc(self, inp, scale, pe):
+        """y = inp * scale + pe[position in the chunk] (asv_posenc_desc_t); pe [positions, channels] float32, built by the caller."""
+        pe = np.ascontiguousarray(pe, dtype=np.float32)
+        if self.seq_spec(inp.tid) is None and self.domain(inp.tid) != DOMAIN_FRAMES:
+            raise TraceError("posenc: frames and sequence tensors only")
+        if pe.ndim != 2 or pe.shape[1] != inp.channels:
+            raise TraceError("posenc: table %s for %d channels" % (pe.shape, inp.channels))
+        out = self.full_view(self.new_tensor(self.domain(inp.tid), inp.channels))
+        self.ops.append(Op("posenc", out, inp=inp, scale=float(np.float32(scale)), pe=pe))
+        return out
+
+    def self_attention(self, q, k, v, heads, d_k):
+        """Multi-head self-attention over the rows of each chunk (asv_self_attention_desc_t): head h = columns [h d_k, (h + 1) d_k) of
+        every view; softmax(q k^T / sqrt(d_k)) v, the heads side by side."""
+        heads, d_k = int(heads), int(d_k)
+        if d_k % 16 != 0 or not 16 <= d_k <= 128:
+            raise TraceError("self_attention: d_k = %d (a multiple of 16 up to 128)" % d_k)
+        dom = self.domain(q.tid)
+        if self.seq_spec(q.tid) is None and dom != DOMAIN_FRAMES:
+            raise TraceError("self_attention: frames and sequence tensors only")
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            if t.channels != heads * d_k or self.domain(t.tid) != dom:
+                raise TraceError("self_attention: %s has %d channels (heads %d x d_k %d) or lives on another domain" % (name, t.channels, heads, d_k))
+        out = self.full_view(self.new_tensor(dom, heads * d_k))
+        self.ops.append(Op("self_attention", out, q=q, k=k, v=v, heads=heads, d_k=d_k))
         return out
 
     def attpool(self, x, logits, eps=1e-5, shared=False, group=0, softplus2=False, prior_logit=None, prior_value=None, mq=None):
@@ -302,6 +383,7 @@ class Graph(object):
 
     def optimize(self):
         self._fold_relu_bn_into_tdnn()
+        self._merge_qkv_projections()
         self._cse_adds()
         self._fold_eltwise_chains()
         self._fold_adds_into_tdnn()
@@ -330,6 +412,33 @@ class Graph(object):
                 continue
             self._replace_tensor(op.out.tid, p.out)
             self.ops.remove(op)
+
+    def _merge_qkv_projections(self):
+        """The q, k and v projections of a self-attention op - three plain 1-tap affines reading ONE tensor, each read by nothing but
+        that op - become ONE affine with the three weight matrices stacked: the normalised rows are read once, one launch instead of
+        three, and the attention op reads three slices of one buffer.  Every output element is the same sum over the same inputs."""
+        for att in [op for op in self.ops if op.kind == "self_attention"]:
+            uses, prod = self._use_count(), self._producer()
+            whole = lambda v: v.ch_off == 0 and v.channels == self.tensors[v.tid][1]
+            ps = [prod.get(v.tid) for v in (att.q, att.k, att.v)]
+            if any(p is None or p.kind != "tdnn" for p in ps) or len({id(p) for p in ps}) != 3:
+                continue
+            plain = lambda p: (p.taps == [0] and p.weight.shape[2] == 1 and p.w_left == 0 and p.inp2 is None and p.act1 is None and p.scale is None and p.act2 is None
+                               and p.seg_bias is None and p.seg_scale is None and p.res is None and not p.affine_first)
+            if not all(plain(p) and whole(v) and uses.get(v.tid, 0) == 1 and p.inp == ps[0].inp for p, v in zip(ps, (att.q, att.k, att.v))):
+                continue
+            if att.q.channels % CHAN_ALIGN != 0 or any((p.bias is None) != (ps[0].bias is None) for p in ps):
+                continue
+            first = min(self.ops.index(p) for p in ps)
+            for p in ps:
+                self.ops.remove(p)
+            n = att.q.channels
+            out = self.full_view(self.new_tensor(self.domain(att.q.tid), 3 * n))
+            merged = Op("tdnn", out, inp=ps[0].inp, inp2=None, weight=np.ascontiguousarray(np.concatenate([p.weight for p in ps], axis=0)),
+                        bias=None if ps[0].bias is None else np.ascontiguousarray(np.concatenate([p.bias.reshape(-1) for p in ps])), taps=[0], w_left=0, act1=None,
+                        scale=None, shift=None, affine_first=False, act2=None, seg_bias=None, seg_scale=None, res=None)
+            self.ops.insert(first, merged)
+            att.q, att.k, att.v = View(out.tid, 0, n), View(out.tid, n, n), View(out.tid, 2 * n, n)
 
     def _is_plain_add(self, op):
         return (op.kind == "eltwise" and op.b is not None and op.c is None and op.seg_scale is None and op.scale is None
@@ -680,6 +789,12 @@ class Graph(object):
                 ins = repr(op.inp)
                 extra = "affine0=%s act0=%s ln=%s%s act1=%s affine1=%s" % (op.scale0 is not None, op.act0, op.ln, "(affine)" if op.gamma is not None else "",
                                                                            op.act1, op.scale1 is not None)
+            elif op.kind == "front_conv":
+                ins, extra = repr(op.inp), "channels=%d" % op.weight.shape[0]
+            elif op.kind == "posenc":
+                ins, extra = repr(op.inp), "scale=%g positions=%d" % (op.scale, op.pe.shape[0])
+            elif op.kind == "self_attention":
+                ins, extra = "q=%r k=%r v=%r" % (op.q, op.k, op.v), "heads=%d d_k=%d" % (op.heads, op.d_k)
             elif op.kind == "eltwise":
                 ins = " ".join("%s=%r" % (n, getattr(op, n)) for n in ("a", "b", "c", "seg_scale") if getattr(op, n) is not None)
                 extra = "affine=%s act=%s" % (op.scale is not None, op.act)

@@ -14,4 +14,8 @@ for _name in _SUBMODULES:
     _mod = _importlib.import_module("." + _name, __name__)
     globals().update({k: v for k, v in vars(_mod).items() if not k.startswith("_")})
 
+# the encoder package exports what the reference's does (libs/nnet/transformer/__init__.py: its __all__)
+_mod = _importlib.import_module(".transformer", __name__)
+globals().update({k: getattr(_mod, k) for k in _mod.__all__})
+
 del _importlib, _name, _mod

@@ -360,6 +360,54 @@ typedef struct asv_grid_conv_desc {
 } asv_grid_conv_desc_t;
 int asv_net_add_grid_conv(asv_net_t *net, const asv_grid_conv_desc_t *d);
 
+/* ---- the transformer encoder (libs/nnet/transformer/, model/transformer_xvector.py; kernels_attention.hip) ---------------- */
+
+/* Grids of the UNPADDED stride-2 subsampling front (Conv2dSubsampling4: Conv2d(kernel 3, stride 2, no padding) twice): a segment of
+ * T frames owns L(T) frames with L the chain n -> (n - 1) / 2 (integer division), applied `time_shift` times, where
+ * asv_net_define_grid() means ceil(T / 2^time_shift).  `width` is given by the caller ((F - 1) / 2 per stage for F bins).  width <
+ * pitch: a grid; width = pitch = 1: the sequence domain behind asv_net_add_grid_flatten.  Everything else is as on a reach-1 grid
+ * (gaps, halo, the row maps every grid op is driven by).  A segment too short to own a row (T < 7 at time_shift 2) is refused by
+ * asv_net_extract.  Domains made by asv_net_define_grid / _reach keep their rule.  Returns the domain id. */
+int asv_net_define_grid_valid(asv_net_t *net, int time_shift, int width, int pitch);
+
+/* First stage of that front as one op: the feature rows [t][f] of frames-domain buffer `in_buf` (feat_dim channels) as a one-channel
+ * image -> out_ch channels on the valid grid of time_shift 1 and width (feat_dim - 1) / 2:
+ *   out[(t', f')][c] = relu(bias[c] + sum_{i, j < 3} weight[c][3 i + j] * in[2 t' + i][2 f' + j])     (i: time, j: frequency)
+ * in the engine's element type, f32 accumulation in tap order.  No full-resolution multi-channel image exists at any point. */
+typedef struct asv_front_conv_desc {
+  uint32_t struct_size;
+  int32_t in_buf, out_buf, out_ch;     /* out_buf: a whole buffer of out_ch channels                       */
+  const float *weight, *bias;          /* host [out_ch][9], [out_ch]                                       */
+} asv_front_conv_desc_t;
+int asv_net_add_front_conv(asv_net_t *net, const asv_front_conv_desc_t *d);
+
+/* out = in * scale + pe[position], position = the row's index inside its segment (it restarts at 0 in every chunk).  pe: host
+ * [pe_rows][channels], copied during the call; a batch with a segment of more than pe_rows - 1 rows is refused by asv_net_extract
+ * (the reference asserts rows < max_len = 5000).  Frames and sequence domains; out may be the input view itself. */
+typedef struct asv_posenc_desc {
+  uint32_t struct_size;
+  int32_t channels;
+  int32_t in_buf, in_ch_off, out_buf, out_ch_off;
+  float   scale;
+  const float *pe;
+  int32_t pe_rows;
+} asv_posenc_desc_t;
+int asv_net_add_posenc(asv_net_t *net, const asv_posenc_desc_t *d);
+
+/* Multi-head self-attention over the rows of each segment: head h takes columns [h * d_k, (h + 1) * d_k) of the q, k and v views
+ * (which may be three slices of one buffer), out[t] = softmax_u(q[t] . k[u] / sqrt(d_k)) . v[u] over the rows u of t's segment
+ * only, heads side by side in the out view in the same column order.  d_k: a multiple of 16 up to 128.  Any segment length: keys
+ * and values stream through LDS in 64-row tiles with an online softmax whose state is f32.  Products on the matrix cores: the
+ * 16-bit instruction in the 16-bit modes (probabilities rounded to the element type for the second product), the exact f32-input
+ * instruction in every f32-storage mode.  The out view must not overlap the q, k or v view.  Frames and sequence domains. */
+typedef struct asv_self_attention_desc {
+  uint32_t struct_size;
+  int32_t q_buf, q_ch_off, k_buf, k_ch_off, v_buf, v_ch_off;
+  int32_t heads, d_k;
+  int32_t out_buf, out_ch_off;
+} asv_self_attention_desc_t;
+int asv_net_add_self_attention(asv_net_t *net, const asv_self_attention_desc_t *d);
+
 /* Freezes the program; `out_buf` must be an utts-domain buffer: its first `embed_dim`
  * channels are the embedding. */
 int asv_net_finalize(asv_net_t *net, int out_buf, int embed_dim);
@@ -407,6 +455,9 @@ int asv_net_status_async(asv_net_t *net, unsigned *host_status, void *stream);
 #define ASV_KERNEL_RES2N 13       /* kernels_res2n.hip: res2n_chain_kernel, the 64-wide Res2 chain as one launch */
 #define ASV_KERNEL_ROWOP 14       /* kernels_rowop.hip: rowop_kernel, the activation / LayerNorm row pass */
 #define ASV_KERNEL_CONV_TAPS 15   /* kernels_conv_taps.hip: grid_conv_taps_kernel, the tap-table grid convolution (asv_net_add_grid_conv) */
+#define ASV_KERNEL_ATTENTION 16   /* kernels_attention.hip: self_attention_kernel (asv_net_add_self_attention) */
+#define ASV_KERNEL_POSENC 17      /* posenc_kernel (asv_net_add_posenc) */
+#define ASV_KERNEL_FRONT_CONV 18  /* front_conv_kernel (asv_net_add_front_conv) */
 unsigned long long asv_kernel_launch_count(int which);
 
 /* Bytes of device memory currently held by the net (weights + activation arena). */
