@@ -8,28 +8,19 @@
 #include <string>
 
 #include "../../include/asv_amd.h"
+#include "batch_plan.h"
 #include "host_convert.h"
 
 namespace asv {
 
 // ---------------------------------------------------------------------------------------
-// error plumbing: nothing throws across the C ABI
-void set_error(const char *fmt, ...);
-
+// error plumbing (set_error and ASV_REQUIRE: batch_plan.h, which the host-only units share)
 #define ASV_HIP_CHECK(expr)                                                                   \
   do {                                                                                        \
     hipError_t _e = (expr);                                                                   \
     if (_e != hipSuccess) {                                                                   \
       ::asv::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
       return ASV_EHIP;                                                                        \
-    }                                                                                         \
-  } while (0)
-
-#define ASV_REQUIRE(cond, ...)                                                                \
-  do {                                                                                        \
-    if (!(cond)) {                                                                            \
-      ::asv::set_error(__VA_ARGS__);                                                          \
-      return ASV_EINVAL;                                                                      \
     }                                                                                         \
   } while (0)
 
@@ -65,16 +56,7 @@ struct DeviceGuard {
 
 static inline int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-// ---------------------------------------------------------------------------------------
-// Row layout of the frames domain (see DESIGN.md "Data layout in HBM").
-//
-// A batch of S utterance segments is laid out as
-//     [HALO zero rows][seg 0][HALO zero rows][seg 1] ... [seg S-1][HALO zero rows][zero fill to R_pad]
-// so a tap that reaches up to HALO frames across a segment edge reads zeros: exactly the
-// per-layer zero padding of TdnnAffine (components.py:116-117), with no masks in the GEMM
-// main loop.  Every producer writes zeros into gap rows (row_valid bit clear).
-constexpr int kHalo = 4;           // max |tap offset| supported (ECAPA dilation 4)
-constexpr int kRowTile = 256;      // rows are padded to a multiple of the largest GEMM M tile
+// the row layout of the frames domain, kHalo and kRowTile: batch_plan.h
 constexpr int kChanAlign = 16;     // channel pitch granularity (elements)
 
 // ---------------------------------------------------------------------------------------
@@ -104,7 +86,7 @@ struct TdnnKernelParams {
   const void *wlo;      // pooled-domain layers and the f32x frame kernel: the bf16 'lo' halves (w - hi), same layout as wfrag, or nullptr
   const void *wx3p;     // f32x 8-phase kernel (kernels_tdnn_p8x.hip): [cout_pad][tap][chunk32][hi 32 | lo 32] 16-bit halves of w * 2^s, or nullptr
   int x_image, y_image; // f32m form: the input rows are / the output rows become IMAGES - per (row, 32-channel group) the 128 bytes [hi halves | x_lo8 | x_hi8]
-                        // the readers' window conversion would make of the f32 values (kernels_tdnn_x3m.hip's epilogue; run_ops decides per buffer and run)
+                        // the readers' window conversion would make of the f32 values (kernels_tdnn_x3m.hip's epilogue; run_tdnn_layer decides per buffer and run)
   const void *w8;       // f32m form (kernels_tdnn_x3m.hip): 8-bit fragments of w * 2^s, planes [w_lo8][w_hi8] (pack_tdnn_weight_mx8), or nullptr
   // split-K (small-M layers: the pooled domain): blockIdx.y walks `ksplit` slices of the channel
   // chunks, raw f32 accumulators go to partial[slice][rows][ld_partial]; a second kernel sums

@@ -31,7 +31,7 @@ correctly rounded implementation could; the host test asks the quarter of the ar
 the rounded read-out to the cap itself.  Measured on the MI355X: bf16 <= 1.50e-03, f16 <= 3.09e-04 (std block, 0.63 of the cap).
 
 Batches: a dozen or so ragged utterances, 1-, 2- and 3-frame ones between utterances of 20 - 40 frames.  A grid segment of T
-frames owns T * pitch rows (pitch = F + 1) and pitch + 2 gap rows lie around it (Domain::gap() in runtime.hip); row_layout()
+frames owns T * pitch rows (pitch = F + 1) and pitch + 2 gap rows lie around it (Domain::gap() in batch_plan.h); row_layout()
 restates that rule and LENS holds, per (F, tile), lengths for which tile seams fall inside short utterances, on the first row of
 an utterance and inside a gap (seam_report(); asserted on the host).
 """

@@ -185,7 +185,7 @@ def _synth_xvector():
 @pytest.mark.parametrize("lens", [[200] * 256, [200] * 255 + [37], list(range(60, 316))], ids=["256x200", "short_last", "ragged_60_315"])
 def test_image_rows_between_f32m_layers_change_no_bit(lens, monkeypatch):
     """The hand-over of activations as IMAGES (the [hi halves | x_lo8 | x_hi8] split made once in the producing layer's epilogue instead of
-    per workgroup and chunk in the readers: kernels_tdnn_x3m.hip, TdnnKernelParams::y_image / x_image, run_ops' reader_takes_image) is the
+    per workgroup and chunk in the readers: kernels_tdnn_x3m.hip, TdnnKernelParams::y_image / x_image, net_run.hip's reader_takes_image) is the
     same arithmetic in another place: tdnn1 -> tdnn2 -> chain of configs[1]'s x-vector with it (two image launches per pass, counted) and
     without it (ASV_AMD_X3M_IMAGE=0) must agree to the last bit, on whole and ragged batches."""
     from libs.amd import capi, synth
@@ -257,7 +257,7 @@ def test_range_watch_through_the_image_epilogue_at_full_size():
 
 
 def test_image_handover_decisions_over_random_batches(monkeypatch):
-    """The producer decides the hand-over by PREDICTING its reader's kernel (run_ops: reader_takes_image); a reader that finds images it cannot
+    """The producer decides the hand-over by PREDICTING its reader's kernel (net_run.hip: reader_takes_image); a reader that finds images it cannot
     read fails the call.  40 seeded batches across the sizes where the selection rules flip (the 8-bit kernel from 384 tiles of 128 x 256 on,
     the 8-phase kernel's whole-rounds rule, short / long / tiny utterances, chained and un-chained): no call may fail, and with and without the
     hand-over the embeddings are the same bits."""

@@ -1,7 +1,7 @@
 """Every host-side weight layout (csrc/weight_pack.cpp) on the CPU: tests/weight_pack_main.cpp is built with g++ twice (-O2, and
 -O1 with the address and undefined-behaviour sanitizers), every case runs through both, and the bytes must equal the digests of
 tests/golden/weight_pack_digests.json - recorded from the packers as they stood before they were rewritten on the shared walker
-(their loops moved verbatim out of runtime.hip / kernels_conv2d_x3.hip / kernels_conv_taps.hip), so the byte order the kernels
+(their loops moved verbatim out of the host runtime (now net_build.hip) / kernels_conv2d_x3.hip / kernels_conv_taps.hip), so the byte order the kernels
 read is pinned.  Besides the digests: the output length is the layout's size function, restated here (where a packer fills a
 caller's buffer the driver pre-fills it with 0xa5: the packer must write all of it), and for two layouts the place of every
 element is restated in numpy from the layout comment, all else being zero."""
