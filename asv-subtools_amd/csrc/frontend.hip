@@ -5,7 +5,9 @@
 // host-side tables below follow line by line (that code is compiled in place as the parity reference, oracle/Makefile.ref).
 //
 // Also here: MFCC output (feature-mfcc.cc), 16-bit PCM input, per-utterance and Kaldi sliding-window CMVN, the energy VAD of
-// runtime/extractor/torch_asv_extractor.cc:14-62 and voiced-frame selection.
+// runtime/extractor/torch_asv_extractor.cc:14-62 and voiced-frame selection; spectrogram output (feature-spectrogram.cc) and PLP
+// (feature-plp.cc): the KIND instantiations of the two feature kernels below, PLP's stopping at the autocorrelations, and
+// plp_lpc_kernel, one lane per frame, for Durbin's recursion and the LPC-to-cepstrum step the reference runs on the CPU.
 //
 // Two feature kernels, one wave per frame in both:
 //   fbank512_kernel  16 kHz windows (257..512 samples): samples, window, pre-emphasis and a radix-4 Stockham FFT in
@@ -56,6 +58,12 @@ struct FbankKernelParams {
   const float *dct;             // [num_ceps][num_bins], rows scaled by the lifter
   float c0_scale;               // sqrt 2 for htk_compat without energy, else 1
   float *out;                   // [total_frames][dim]
+  // PLP (KIND == ASV_FEAT_PLP): the feature kernels stop at the autocorrelations, plp_lpc_kernel finishes the frame
+  int lpc_order;
+  float compress;
+  const float *eql;             // [num_bins] equal-loudness weights of the bin centres
+  const float *idft_t;          // [num_bins + 2][lpc_order + 1]: InitIdftBases, transposed (lane = coefficient reads contiguously)
+  float *acorr;                 // [lpc_order + 2][total_frames]: autocorrelations 0 .. lpc_order, then the floored log energy
 };
 
 // Sum over the 64 lanes, the same value in every lane: four DPP steps inside each row of 16 (quad xor 1, quad xor 2,
@@ -72,6 +80,27 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 
+// orders a wave's LDS writes before its following LDS reads of other lanes' data (no instruction beyond the wait)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// PLP, feature-plp.cc:121-138, from the mel energies to the autocorrelations.  plp_compress: one mel energy x equal loudness,
+// pow(compress_factor).  The caller stores the values of all bins at ext[1 + b], the first and the last a second time at ext[0]
+// and ext[num_bins + 1], and orders those writes (wave_lds_sync); plp_autocorr is then lane = coefficient: row c of the IDFT
+// matrix times ext, summed in index order.  Column lpc_order + 1 of the buffer takes the frame's floored log energy.
+__device__ __forceinline__ float plp_compress(const FbankKernelParams &p, float mel, int b) { return powf(mel * p.eql[b], p.compress); }
+__device__ __forceinline__ void plp_autocorr(const FbankKernelParams &p, const float *ext, float log_energy, long long frame, int lane) {
+  const int nc = p.lpc_order + 1, n = p.num_bins + 2;
+  for (int c = lane; c < nc; c += 64) {
+    float acc = 0.0f;
+    for (int j = 0; j < n; ++j) acc = fmaf(ext[j], p.idft_t[(size_t)j * nc + c], acc);
+    p.acorr[(size_t)c * p.total_frames + frame] = acc;
+  }
+  if (lane == 0) p.acorr[(size_t)nc * p.total_frames + frame] = fmaxf(log_energy, p.log_energy_floor);
+}
+
 // Cepstra of one frame from its log mel energies in LDS (feature-mfcc.cc:118-148): lane c sums row c of the liftered DCT
 // matrix; C0 is replaced by the log energy when asked for; htk_compat rotates C0 / the energy to the last column.
 __device__ __forceinline__ void write_cepstra(const FbankKernelParams &p, const float *logmel, float log_energy, float *dst, int lane) {
@@ -84,7 +113,7 @@ __device__ __forceinline__ void write_cepstra(const FbankKernelParams &p, const 
   }
 }
 
-template <typename SAMPLE>
+template <typename SAMPLE, int KIND = ASV_FEAT_FBANK>
 __global__ __launch_bounds__(256) void fbank_kernel(const FbankKernelParams p) {
   extern __shared__ float lds[];                       // per wave: re[padded] | im[padded]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -163,6 +192,15 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankKernelParams p) {
       re[base + span] = ar - tr; im[base + span] = ai - ti;
     }
   }
+  if constexpr (KIND == ASV_FEAT_SPECTROGRAM) {
+    // feature-spectrogram.cc:39-61: log power of bins 0 .. N/2, the Nyquist bin included; column 0 is the log energy
+    float *row = p.out + (size_t)frame * (half + 1);
+    for (int i = lane; i <= half; i += 64) {
+      const float pw = re[i] * re[i] + im[i] * im[i];
+      row[i] = i == 0 ? fmaxf(log_energy, p.log_energy_floor) : logf(fmaxf(pw, 1.1920928955078125e-07f));
+    }
+    return;
+  }
   // spectrum of bins 0 .. N/2 - 1 (the reference drops the Nyquist bin, feature-fbank.cc:66-68)
   for (int i = lane; i < half; i += 64) {
     const float pw = re[i] * re[i] + im[i] * im[i];
@@ -176,9 +214,21 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankKernelParams p) {
     const int i0 = p.mel_first[b], cnt = p.mel_count[b];
     float acc = 0.0f;
     for (int k = 0; k < cnt; ++k) acc = fmaf(re[i0 + k], w[k], acc);
+    if constexpr (KIND == ASV_FEAT_PLP) {
+      acc = plp_compress(p, acc, b);
+      im[1 + b] = acc;                                   // the FFT's imaginary parts are consumed; num_bins + 2 <= padded
+      if (b == 0) im[0] = acc;
+      if (b == p.num_bins - 1) im[p.num_bins + 1] = acc;
+      continue;
+    }
     if (take_log) acc = logf(fmaxf(acc, 1.1920928955078125e-07f));
     if (p.num_ceps > 0) im[b] = acc;
     else dst[b + ((p.use_energy && !p.htk_compat) ? 1 : 0)] = acc;
+  }
+  if constexpr (KIND == ASV_FEAT_PLP) {
+    wave_lds_sync();
+    plp_autocorr(p, im, log_energy, frame, lane);
+    return;
   }
   if (p.num_ceps > 0) { write_cepstra(p, im, log_energy, dst, lane); return; }
   if (p.use_energy && lane == 0) dst[p.htk_compat ? p.num_bins : 0] = fmaxf(log_energy, p.log_energy_floor);
@@ -201,11 +251,6 @@ __device__ __forceinline__ void dft4(cplx v[4]) {
   v[0] = {a0.x + a2.x, a0.y + a2.y}; v[1] = {a1.x + a3.x, a1.y + a3.y};
   v[2] = {a0.x - a2.x, a0.y - a2.y}; v[3] = {a1.x - a3.x, a1.y - a3.y};
 }
-// orders a wave's LDS writes before its following LDS reads of other lanes' data (no instruction beyond the wait)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 // Exchange buffer indices (float2 slots).  A ds_write_b64 is served 16 consecutive lanes at a time over 32 banks, so the
 // 16 slots of a lane group must differ mod 16; the reads (lane + 64 r) stay contiguous per 32 lanes under each padding.
 //   pass 1 writes 4 j + r, pass 2 writes 16 (j / 4) + j % 4 + 4 r, pass 3 writes 64 (j / 16) + j % 16 + 16 r.
@@ -219,7 +264,7 @@ __device__ __forceinline__ cplx tw512(const float2 *t, int idx) {          // W5
 
 constexpr int kFastMaxSeg = 256;     // mel filter segments (<= 8 FFT bins each) the kernel has room for: 4 lanes-passes
 
-template <bool MFCC, typename SAMPLE>
+template <bool MFCC, typename SAMPLE, int KIND = ASV_FEAT_FBANK>
 __global__ __launch_bounds__(256) void fbank512_kernel(const FbankKernelParams p) {
   __shared__ float2 xch[4][320];          // 256 points (padded to 316 slots); later |X|^2 [256] + 8 zeros + segment sums [256]
   __shared__ float4 segw[2][kFastMaxSeg];
@@ -372,8 +417,17 @@ __global__ __launch_bounds__(256) void fbank512_kernel(const FbankKernelParams p
       const cplx od = cmul(cplx{d.y, -d.x}, ts[r]);                          // -i d W512^k
       const float xr = ev.x + od.x, xi = ev.y + od.y;
       const float pwr = xr * xr + xi * xi;
+      if constexpr (KIND == ASV_FEAT_SPECTROGRAM) {
+        // feature-spectrogram.cc:39-61; bin 0 gives way to the log energy.  The Nyquist bin, which the split step does not
+        // produce, is real: X[256] = Re Z[0] - Im Z[0], held by lane 0.
+        float *row = p.out + (size_t)frame * 257;
+        row[lane + 64 * r] = (r == 0 && lane == 0) ? fmaxf(log_energy, p.log_energy_floor) : logf(fmaxf(pwr, 1.1920928955078125e-07f));
+        if (r == 0 && lane == 0) { const float ny = v[0].x - v[0].y; row[256] = logf(fmaxf(ny * ny, 1.1920928955078125e-07f)); }
+        continue;
+      }
       pw[lane + 64 * r] = (MFCC || p.use_power) ? pwr : sqrtf(pwr);                    // overwrites pass-4 inputs, already consumed
     }
+    if constexpr (KIND == ASV_FEAT_SPECTROGRAM) continue;                    // nothing of this frame is left in LDS
     if (lane < 8) pw[256 + lane] = 0.0f;
     wave_lds_sync();
     // mel filters: one lane per segment of <= 8 FFT bins, partial sums to LDS, then one lane per mel bin adds its segments
@@ -392,15 +446,79 @@ __global__ __launch_bounds__(256) void fbank512_kernel(const FbankKernelParams p
       const int s_lo = p.bin_seg[b], s_hi = p.bin_seg[b + 1];
       float acc = part[s_lo];
       for (int sg = s_lo + 1; sg < s_hi; ++sg) acc += part[sg];
+      if constexpr (KIND == ASV_FEAT_PLP) {
+        acc = plp_compress(p, acc, b);
+        pw[1 + b] = acc;                                           // |X|^2 is consumed; num_bins + 2 <= 258 < 264, where `part` begins
+        if (b == 0) pw[0] = acc;
+        if (b == p.num_bins - 1) pw[p.num_bins + 1] = acc;
+        continue;
+      }
       if (take_log) acc = logf(fmaxf(acc, 1.1920928955078125e-07f));
       if (MFCC) pw[b] = acc;                                       // |X|^2 is consumed; num_bins <= 256 here
       else dst[b + ((p.use_energy && !p.htk_compat) ? 1 : 0)] = acc;
     }
-    if (MFCC) {
+    if constexpr (KIND == ASV_FEAT_PLP) {
+      wave_lds_sync();
+      plp_autocorr(p, pw, log_energy, frame, lane);
+    } else if (MFCC) {
       wave_lds_sync();
       write_cepstra(p, pw, log_energy, dst, lane);
     } else if (p.use_energy && lane == 0) dst[p.htk_compat ? p.num_bins : 0] = fmaxf(log_energy, p.log_energy_floor);
     wave_lds_sync();                                                         // the next frame's pass 1 overwrites pw
+  }
+}
+
+// ---- PLP tail: autocorrelations -> LPC -> cepstra (mel-computations.cc:229-321, feature-plp.cc:141-181) ------------------
+// One LANE per frame, 64 frames per wave, one wave per workgroup.  Durbin's recursion and the LPC-to-cepstrum recursion are
+// sequential and ill-conditioned, so every lane runs the reference's statements in the reference's order, every operation
+// rounded on its own (no FMA contraction), the cepstrum's inner sum in double as there.  pLP lives in LDS as [index][lane]
+// (dynamic index, conflict-free: a wave reads 64 consecutive floats); pTmp and, once Durbin is done, the cepstra share the
+// second array.  The autocorrelations are read where kernel one left them, [coefficient][frame]: coalesced, L1/L2 hits.
+// Dynamic LDS: 2 * lpc_order * 64 floats (<= 31.5 KiB at order 63).
+struct PlpTailParams {
+  const float *acorr;           // [lpc_order + 2][total_frames]
+  long long total_frames;
+  int lpc_order, num_ceps, use_energy, htk_compat;
+  const float *lifter;          // [num_ceps], nullptr: no lifter
+  float scale;                  // cepstral_scale
+  float *out;                   // [total_frames][num_ceps]
+};
+
+__global__ __launch_bounds__(64) void plp_lpc_kernel(const PlpTailParams p) {
+#pragma clang fp contract(off)
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x, n = p.lpc_order;
+  const long long frame = (long long)blockIdx.x * 64 + lane;
+  if (frame >= p.total_frames) return;
+  float *pLP = lds + lane, *pTmp = lds + (size_t)n * 64 + lane;                // element k of this frame: [k * 64]
+  const float *pAC = p.acorr + frame;                                         // element k: [k * total_frames]
+  const size_t T = (size_t)p.total_frames;
+  float E = pAC[0];
+  for (int i = 0; i < n; ++i) {
+    float ki = pAC[(size_t)(i + 1) * T];
+    for (int j = 0; j < i; ++j) ki += pLP[j * 64] * pAC[(size_t)(i - j) * T];
+    ki = ki / E;
+    float c = 1 - ki * ki;
+    if (c < 1.0e-5) c = 1.0e-5;
+    E *= c;
+    pTmp[i * 64] = -ki;
+    for (int j = 0; j < i; ++j) pTmp[j * 64] = pLP[j * 64] - ki * pLP[(i - j - 1) * 64];
+    for (int j = 0; j <= i; ++j) pLP[j * 64] = pTmp[j * 64];
+  }
+  const float c0 = fmaxf(-logf((float)(1.0 / E)), 1.1920928955078125e-07f);   // feature-plp.cc:143 clamps the "residual log energy" itself
+  float *pCepst = pTmp;
+  for (int i = 0; i < n; ++i) {
+    double sum = 0.0;
+    for (int j = 0; j < i; ++j) sum += (i - j) * pLP[j * 64] * pCepst[(i - j - 1) * 64];
+    pCepst[i * 64] = -pLP[i * 64] - sum / (i + 1);
+  }
+  float *dst = p.out + (size_t)frame * p.num_ceps;
+  for (int k = 0; k < p.num_ceps; ++k) {
+    float v = k == 0 ? c0 : pCepst[(k - 1) * 64];
+    if (p.lifter) v = v * p.lifter[k];
+    if (p.scale != 1.0f) v = v * p.scale;
+    if (k == 0 && p.use_energy) v = pAC[(size_t)(n + 1) * T];
+    dst[p.htk_compat ? (k == 0 ? p.num_ceps - 1 : k - 1) : k] = v;
   }
 }
 
@@ -584,7 +702,7 @@ struct OffsetCache {
 };
 thread_local OffsetCache g_fbank_offs, g_cmvn_offs;
 
-struct FrontTables { float *dct; float *window; float2 *twiddle; float *mel_w; int *mel_first, *mel_count; int mel_stride; float *seg_w; int *seg_first, *bin_seg; int n_seg; };
+struct FrontTables { float *dct; float *window; float2 *twiddle; float *mel_w; int *mel_first, *mel_count; int mel_stride; float *seg_w; int *seg_first, *bin_seg; int n_seg; float *eql, *idft_t, *lifter; };
 thread_local FrontTables g_tab = {};
 
 int window_size(const asv_fbank_opts_t &o, float ms) { return (int)(o.sample_rate * 0.001f * ms); }
@@ -596,20 +714,115 @@ using namespace asv;
 
 extern "C" {
 
+// The options block as the library reads it: a caller's block of either known size, the fields it does not have zeroed
+// (feature_kind 0), and for PLP the zero "defaults" of the header replaced by the reference's values.
+static bool normalise_opts(const asv_fbank_opts_t *in, asv_fbank_opts_t *o) {
+  if (!in || (in->struct_size != sizeof(asv_fbank_opts_t) && in->struct_size != ASV_FBANK_OPTS_SIZE_V1)) return false;
+  memset(o, 0, sizeof(*o));
+  memcpy(o, in, in->struct_size);
+  o->struct_size = sizeof(*o);
+  if (o->feature_kind == ASV_FEAT_PLP) {
+    if (o->num_ceps == 0) o->num_ceps = 13;
+    if (o->lpc_order == 0) o->lpc_order = 12;
+    if (o->compress_factor == 0.0f) o->compress_factor = 0.33333f;
+    if (o->cepstral_scale == 0.0f) o->cepstral_scale = 1.0f;
+  }
+  return true;
+}
+
+static int padded_window(const asv_fbank_opts_t &o) {
+  const int length = window_size(o, o.frame_length_ms);
+  int pw = 1;
+  while (pw < length) pw *= 2;
+  return pw;
+}
+
+int asv_fbank_dim(const asv_fbank_opts_t *opts) {
+  asv_fbank_opts_t o;
+  if (!normalise_opts(opts, &o)) return -1;
+  switch (o.feature_kind) {
+    case ASV_FEAT_FBANK: return o.num_ceps > 0 ? o.num_ceps : (o.num_bins >= 1 ? o.num_bins + (o.use_energy ? 1 : 0) : -1);
+    case ASV_FEAT_PLP: return (o.lpc_order >= 1 && o.lpc_order <= ASV_PLP_MAX_LPC_ORDER && o.num_ceps >= 1 && o.num_ceps <= o.lpc_order + 1) ? o.num_ceps : -1;
+    case ASV_FEAT_SPECTROGRAM: {
+      const int length = window_size(o, o.frame_length_ms);
+      return (length >= 2 && length <= kMaxFft) ? padded_window(o) / 2 + 1 : -1;
+    }
+    default: return -1;
+  }
+}
+
 long long asv_fbank_num_frames(const asv_fbank_opts_t *o, long long num_samples) {
-  if (!o || o->struct_size != sizeof(asv_fbank_opts_t)) return -1;
+  if (!o || (o->struct_size != sizeof(asv_fbank_opts_t) && o->struct_size != ASV_FBANK_OPTS_SIZE_V1)) return -1;
   const long long length = window_size(*o, o->frame_length_ms), shift = window_size(*o, o->frame_shift_ms);
   if (length <= 0 || shift <= 0) return -1;
   if (o->snip_edges) return num_samples < length ? 0 : 1 + (num_samples - length) / shift;
   return (num_samples + shift / 2) / shift;
 }
 
-static int fbank_entry(const asv_fbank_opts_t *o, const void *wave, bool pcm16, const long long *sample_offsets, int n_utts, float *feats, void *stream) {
-  ASV_REQUIRE(o && o->struct_size == sizeof(asv_fbank_opts_t), "asv_fbank: struct_size mismatch");
+// Spectrogram and PLP launches: the KIND instantiations of the two feature kernels, chosen like the filterbank ones (the
+// 512-point kernel where it applies); PLP then runs plp_lpc_kernel over the autocorrelation buffer in between (stream-ordered
+// allocation, freed behind the second launch).
+static int launch_kind(const asv_fbank_opts_t &o, FbankKernelParams p, bool pcm16, hipStream_t s) {
+  const long long total = p.total_frames;
+  const bool plp = o.feature_kind == ASV_FEAT_PLP;
+  float *acorr = nullptr;
+  if (plp) {
+    ASV_REQUIRE(o.num_bins + 2 <= p.padded, "asv_fbank: num_bins %d + 2 values do not fit a %d-point frame", o.num_bins, p.padded);
+    ASV_HIP_CHECK(hipMallocAsync(reinterpret_cast<void **>(&acorr), (size_t)(o.lpc_order + 2) * (size_t)total * sizeof(float), s));
+    p.lpc_order = o.lpc_order; p.compress = o.compress_factor; p.eql = g_tab.eql; p.idft_t = g_tab.idft_t; p.acorr = acorr;
+  }
+  if (p.padded == 512 && g_tab.n_seg <= kFastMaxSeg && o.num_bins <= 256) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const long long waves = (long long)cus * 4 * 4;
+    p.fpw = (int)std::max<long long>(4, (total + waves - 1) / waves);
+    const long long per_wg = 4LL * p.fpw;
+    const dim3 grid((unsigned)((total + per_wg - 1) / per_wg));
+    if (plp && pcm16) hipLaunchKernelGGL((fbank512_kernel<false, short, ASV_FEAT_PLP>), grid, dim3(256), 0, s, p);
+    else if (plp) hipLaunchKernelGGL((fbank512_kernel<false, float, ASV_FEAT_PLP>), grid, dim3(256), 0, s, p);
+    else if (pcm16) hipLaunchKernelGGL((fbank512_kernel<false, short, ASV_FEAT_SPECTROGRAM>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((fbank512_kernel<false, float, ASV_FEAT_SPECTROGRAM>), grid, dim3(256), 0, s, p);
+  } else {
+    const size_t lds_bytes = (size_t)4 * 2 * p.padded * 4;
+    const dim3 grid((unsigned)((total + 3) / 4));
+    if (plp && pcm16) hipLaunchKernelGGL((fbank_kernel<short, ASV_FEAT_PLP>), grid, dim3(256), lds_bytes, s, p);
+    else if (plp) hipLaunchKernelGGL((fbank_kernel<float, ASV_FEAT_PLP>), grid, dim3(256), lds_bytes, s, p);
+    else if (pcm16) hipLaunchKernelGGL((fbank_kernel<short, ASV_FEAT_SPECTROGRAM>), grid, dim3(256), lds_bytes, s, p);
+    else hipLaunchKernelGGL((fbank_kernel<float, ASV_FEAT_SPECTROGRAM>), grid, dim3(256), lds_bytes, s, p);
+  }
+  ASV_HIP_CHECK(hipGetLastError());
+  if (plp) {
+    PlpTailParams t;
+    t.acorr = acorr; t.total_frames = total; t.lpc_order = o.lpc_order; t.num_ceps = o.num_ceps; t.use_energy = o.use_energy; t.htk_compat = o.htk_compat;
+    t.lifter = g_tab.lifter; t.scale = o.cepstral_scale; t.out = p.out;
+    hipLaunchKernelGGL(plp_lpc_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), (size_t)2 * o.lpc_order * 64 * sizeof(float), s, t);
+    ASV_HIP_CHECK(hipGetLastError());
+    ASV_HIP_CHECK(hipFreeAsync(acorr, s));
+  }
+  return ASV_OK;
+}
+
+static int fbank_entry(const asv_fbank_opts_t *opts_in, const void *wave, bool pcm16, const long long *sample_offsets, int n_utts, float *feats, void *stream) {
+  asv_fbank_opts_t full;
+  ASV_REQUIRE(normalise_opts(opts_in, &full), "asv_fbank: struct_size mismatch");
+  if (full.feature_kind == ASV_FEAT_SPECTROGRAM) {
+    // the fields a spectrogram does not read take fixed values: one set of tables per framing, and a mel table nobody uses
+    full.num_bins = 3; full.low_freq = 0.0f; full.high_freq = 0.0f; full.num_ceps = 0; full.vtln_warp = 1.0f; full.use_energy = 1; full.htk_compat = 0;
+  }
+  const asv_fbank_opts_t *o = &full;
+  const int kind = o->feature_kind;
   ASV_REQUIRE(wave && sample_offsets && feats && n_utts >= 1, "asv_fbank: bad argument");
-  ASV_ON_OWNER(feats, "asv_fbank");
+  ASV_REQUIRE(kind == ASV_FEAT_FBANK || kind == ASV_FEAT_SPECTROGRAM || kind == ASV_FEAT_PLP, "asv_fbank: feature_kind %d", kind);
+  ASV_REQUIRE(o->return_raw_fft == 0, "asv_fbank: return_raw_fft is not supported (the reference refuses it too)");
   ASV_REQUIRE(o->num_bins >= 3 && o->num_bins <= 512, "asv_fbank: num_bins %d", o->num_bins);
-  ASV_REQUIRE(o->num_ceps >= 0 && o->num_ceps <= o->num_bins, "asv_fbank: num_ceps %d must not exceed num_bins %d", o->num_ceps, o->num_bins);
+  if (kind == ASV_FEAT_PLP) {
+    ASV_REQUIRE(o->lpc_order >= 1 && o->lpc_order <= ASV_PLP_MAX_LPC_ORDER, "asv_fbank: lpc_order %d is outside [1, %d]", o->lpc_order, ASV_PLP_MAX_LPC_ORDER);
+    ASV_REQUIRE(o->num_ceps >= 1 && o->num_ceps <= o->lpc_order + 1, "asv_fbank: num_ceps %d must not exceed lpc_order + 1 = %d", o->num_ceps, o->lpc_order + 1);
+    ASV_REQUIRE(o->compress_factor > 0.0f, "asv_fbank: compress_factor %g must be positive", o->compress_factor);
+  } else {
+    ASV_REQUIRE(o->num_ceps >= 0 && o->num_ceps <= o->num_bins, "asv_fbank: num_ceps %d must not exceed num_bins %d", o->num_ceps, o->num_bins);
+  }
+  ASV_ON_OWNER(feats, "asv_fbank");                        // (every refusal above is decided from the options alone)
   ASV_REQUIRE(o->window_type >= ASV_WINDOW_POVEY && o->window_type <= ASV_WINDOW_BLACKMAN, "asv_fbank: window type %d", o->window_type);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int length = window_size(*o, o->frame_length_ms), shift = window_size(*o, o->frame_shift_ms);
@@ -673,10 +886,12 @@ static int fbank_entry(const asv_fbank_opts_t *o, const void *wave, bool pcm16, 
     const float mel_low = mel_scale(o->low_freq), mel_high = mel_scale(high);
     const float delta = (mel_high - mel_low) / (o->num_bins + 1);
     std::vector<int> first(o->num_bins, -1), count(o->num_bins, 0);
+    std::vector<float> centre_freq(o->num_bins);         // of the (warped) bin centres, mel-computations.cc:162: the equal-loudness curve's argument
     std::vector<std::vector<float>> rows(o->num_bins);
     int stride = 1;
     for (int b = 0; b < o->num_bins; ++b) {
       const float left = warp_mel(mel_low + b * delta), center = warp_mel(mel_low + (b + 1) * delta), right = warp_mel(mel_low + (b + 2) * delta);
+      centre_freq[b] = 700.0f * (expf(center / 1127.0f) - 1.0f);
       int last = -1;
       std::vector<float> dense(n_fft, 0.0f);
       for (int i = 0; i < n_fft; ++i) {
@@ -721,7 +936,31 @@ static int fbank_entry(const asv_fbank_opts_t *o, const void *wave, bool pcm16, 
     if ((rc = up(binseg.data(), binseg.size() * 4, reinterpret_cast<void **>(&g_tab.bin_seg)))) return rc;
     g_tab.n_seg = (int)segk.size();
     g_tab.dct = nullptr;
-    if (o->num_ceps > 0) {
+    g_tab.eql = g_tab.idft_t = g_tab.lifter = nullptr;
+    if (kind == ASV_FEAT_PLP) {
+      // GetEqualLoudnessVector (mel-computations.cc:214-227), InitIdftBases (feature-functions.cc:13-31, stored transposed) and
+      // ComputeLifterCoeffs (mel-computations.cc:203-212), each in the reference's mix of float and double
+      const int nb = o->num_bins, dimension = nb + 2, nc = o->lpc_order + 1;
+      std::vector<float> eql(nb), idft((size_t)dimension * nc), lift(o->num_ceps);
+      for (int b = 0; b < nb; ++b) {
+        const float fsq = centre_freq[b] * centre_freq[b];
+        const float fsub = fsq / (fsq + 1.6e5);
+        eql[b] = fsub * fsub * ((fsq + 1.44e6) / (fsq + 9.61e6));
+      }
+      const float angle = M_PI / (dimension - 1);
+      const float scale = 1.0f / (2 * (dimension - 1));
+      for (int i = 0; i < nc; ++i) {
+        idft[i] = scale;
+        for (int j = 1; j < dimension - 1; ++j) idft[(size_t)j * nc + i] = 2 * scale * cosf(angle * i * j);
+        idft[(size_t)(dimension - 1) * nc + i] = scale * cosf(angle * i * (dimension - 1));
+      }
+      if ((rc = up(eql.data(), eql.size() * 4, reinterpret_cast<void **>(&g_tab.eql)))) return rc;
+      if ((rc = up(idft.data(), idft.size() * 4, reinterpret_cast<void **>(&g_tab.idft_t)))) return rc;
+      if (o->cepstral_lifter != 0.0f) {
+        for (int i = 0; i < o->num_ceps; ++i) lift[i] = 1.0 + 0.5 * o->cepstral_lifter * sin(M_PI * i / o->cepstral_lifter);
+        if ((rc = up(lift.data(), lift.size() * 4, reinterpret_cast<void **>(&g_tab.lifter)))) return rc;
+      }
+    } else if (o->num_ceps > 0) {
       // matrix-functions.cc:15-43 (DCT-II rows, float normalisers, double cosine) x mel-computations.cc:203-212 (lifter)
       const int nb = o->num_bins;
       std::vector<float> dct((size_t)o->num_ceps * nb);
@@ -766,6 +1005,7 @@ static int fbank_entry(const asv_fbank_opts_t *o, const void *wave, bool pcm16, 
   p.mel_first = g_tab.mel_first; p.mel_count = g_tab.mel_count; p.mel_stride = g_tab.mel_stride; p.out = feats;
   p.num_ceps = o->num_ceps; p.dct = g_tab.dct; p.c0_scale = (o->htk_compat && !o->use_energy) ? (float)M_SQRT2 : 1.0f;
   p.seg_w = g_tab.seg_w; p.seg_first = g_tab.seg_first; p.bin_seg = g_tab.bin_seg; p.n_seg = g_tab.n_seg;
+  if (kind != ASV_FEAT_FBANK) return launch_kind(*o, p, pcm16, s);
   static const bool generic_only = getenv("ASV_AMD_FBANK_GENERIC") != nullptr;
   if (padded == 512 && g_tab.n_seg <= kFastMaxSeg && o->num_bins <= 256 && !generic_only) {
     // every wave gets the same number of consecutive frames: enough workgroups for 4 per CU, at least 4 frames each so

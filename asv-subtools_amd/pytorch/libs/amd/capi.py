@@ -215,7 +215,15 @@ class FbankOpts(C.Structure):
         ("use_log_fbank", C.c_int32), ("use_power", C.c_int32),
         ("num_ceps", C.c_int32), ("cepstral_lifter", C.c_float),
         ("blackman_coeff", C.c_float), ("vtln_warp", C.c_float), ("vtln_low", C.c_float), ("vtln_high", C.c_float),
+        # behind FBANK_OPTS_SIZE_V1 (the header's ASV_FBANK_OPTS_SIZE_V1): spectrogram / PLP
+        ("feature_kind", C.c_int32), ("lpc_order", C.c_int32), ("compress_factor", C.c_float), ("cepstral_scale", C.c_float),
+        ("return_raw_fft", C.c_int32),
     ]
+
+
+FBANK_OPTS_SIZE_V1 = 96
+FEATURE_KINDS = {"fbank": 0, "mfcc": 0, "spectrogram": 1, "plp": 2}          # ASV_FEAT_*; MFCC is filterbank output with num_ceps > 0
+PLP_MAX_LPC_ORDER = 63
 
 
 WINDOW_TYPES = {"povey": 0, "hamming": 1, "hanning": 2, "rectangular": 3, "sine": 4, "blackman": 5}
@@ -244,7 +252,7 @@ SYMBOLS = [
     "asv_plda_transform", "asv_plda_llr_trials", "asv_eer", "asv_det_curve", "asv_min_dcf", "asv_cavg", "asv_score_norm", "asv_group_mean", "asv_two_cov_trials",
     "asv_plda_llr_matrix", "asv_two_cov_matrix",
     "asv_plda_train", "asv_scatter_f64", "asv_class_scatter_f64",
-    "asv_fbank_num_frames", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
+    "asv_fbank_num_frames", "asv_fbank_dim", "asv_fbank", "asv_fbank_pcm16", "asv_cmvn", "asv_cmvn_sliding", "asv_vad_energy", "asv_select_frames",
     "asv_ingest_frames", "asv_decode_compressed", "asv_ingest_windows", "asv_desilence_pcm16",
     "asv_net_define_grid_reach", "asv_net_add_grid_conv",
     "asv_net_define_grid_valid", "asv_net_add_front_conv", "asv_net_add_posenc", "asv_net_add_self_attention",
@@ -334,6 +342,7 @@ def lib():
     L.asv_class_scatter_f64.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), ci,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), vp]
     L.asv_fbank_num_frames.argtypes = [C.POINTER(FbankOpts), C.c_longlong]; L.asv_fbank_num_frames.restype = C.c_longlong
+    L.asv_fbank_dim.argtypes = [C.POINTER(FbankOpts)]
     L.asv_fbank.argtypes = [C.POINTER(FbankOpts), vp, C.POINTER(C.c_longlong), ci, vp, vp]
     L.asv_fbank_pcm16.argtypes = [C.POINTER(FbankOpts), vp, C.POINTER(C.c_longlong), ci, vp, vp]
     L.asv_cmvn_sliding.argtypes = [vp, vp, C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp]

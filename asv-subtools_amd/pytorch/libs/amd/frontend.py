@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
-"""Acoustic front-end on the MI355X: Kaldi-compatible log-mel filterbank features (+ per-utterance mean/variance
-normalisation) of a batch of waveforms in one launch, through asv_fbank / asv_cmvn of libasv_amd.so.
+"""Acoustic front-end on the MI355X: Kaldi-compatible log-mel filterbank, MFCC, PLP and spectrogram features (+ per-utterance
+mean/variance normalisation) of a batch of waveforms in one launch (PLP: two), through asv_fbank / asv_cmvn of libasv_amd.so.
 
 Replaces the per-utterance torchaudio.compliance.kaldi.fbank loop of reference
 pytorch/libs/egs/kaldi_features.py:107-137 (and kaldifeat::Fbank of runtime/kaldifeat/csrc); option names and defaults
@@ -25,9 +25,32 @@ _DEFAULTS = dict(
 _MFCC_DEFAULTS = dict({k: v for k, v in _DEFAULTS.items() if k not in ("use_log_fbank", "use_power")}, num_ceps=13, cepstral_lifter=22.0)
 
 
+# PLP (reference runtime/kaldifeat/csrc/feature-plp.h PlpOptions; torchaudio has no PLP): the framing / mel names of above, the
+# cepstral ones of mfcc, plus lpc_order / compress_factor / cepstral_scale.  use_energy and energy_floor default as PlpOptions does.
+_PLP_DEFAULTS = dict(_MFCC_DEFAULTS, use_energy=True, energy_floor=0.0, lpc_order=12, compress_factor=0.33333, cepstral_scale=1.0)
+
+# torchaudio.compliance.kaldi.spectrogram (= feature-spectrogram.h SpectrogramOptions): framing options and the energy in column 0
+_SPECTROGRAM_DEFAULTS = dict({k: _DEFAULTS[k] for k in (
+    "blackman_coeff", "channel", "dither", "energy_floor", "frame_length", "frame_shift", "min_duration", "preemphasis_coefficient", "raw_energy",
+    "remove_dc_offset", "round_to_power_of_two", "sample_frequency", "snip_edges", "subtract_mean", "window_type")}, return_raw_fft=False)
+
+_KIND_DEFAULTS = {"fbank": _DEFAULTS, "mfcc": _MFCC_DEFAULTS, "plp": _PLP_DEFAULTS, "spectrogram": _SPECTROGRAM_DEFAULTS}
+
+
+def _padded_window(o):
+    length = int(np.float32(o["sample_frequency"]) * np.float32(0.001) * np.float32(o["frame_length"]))
+    padded = 1
+    while padded < length:
+        padded *= 2
+    return padded
+
+
 def fbank_options(_kind="fbank", **kw):
-    """A filled asv_fbank_opts_t from torchaudio-style keywords; refuses what the device path does not compute."""
-    defaults = _DEFAULTS if _kind == "fbank" else _MFCC_DEFAULTS
+    """A filled asv_fbank_opts_t from torchaudio-style keywords; refuses what the device path does not compute.
+    _kind: "fbank", "mfcc", "plp" or "spectrogram"."""
+    if _kind not in _KIND_DEFAULTS:
+        raise ValueError("unknown feature kind %r (one of %s)" % (_kind, sorted(_KIND_DEFAULTS)))
+    defaults = _KIND_DEFAULTS[_kind]
     unknown = set(kw) - set(defaults)
     if unknown:
         raise TypeError("%s: unknown option(s) %s" % (_kind, sorted(unknown)))
@@ -36,9 +59,29 @@ def fbank_options(_kind="fbank", **kw):
     o.setdefault("use_power", True)
     o.setdefault("num_ceps", 0)
     o.setdefault("cepstral_lifter", 0.0)
-    o["dim"] = o["num_ceps"] if _kind == "mfcc" else o["num_mel_bins"] + int(o["use_energy"])
+    for k in ("htk_compat", "use_energy", "vtln_high", "vtln_low", "vtln_warp", "low_freq", "high_freq", "num_mel_bins"):      # (spectrogram has none of these)
+        o.setdefault(k, _DEFAULTS[k])
+    o.setdefault("lpc_order", 0)
+    o.setdefault("compress_factor", 0.0)
+    o.setdefault("cepstral_scale", 0.0)
+    o.setdefault("return_raw_fft", False)
+    if _kind == "spectrogram":
+        o["dim"] = _padded_window(o) // 2 + 1
+    else:
+        o["dim"] = o["num_ceps"] if _kind in ("mfcc", "plp") else o["num_mel_bins"] + int(o["use_energy"])
     if _kind == "mfcc" and not 1 <= o["num_ceps"] <= o["num_mel_bins"]:
         raise ValueError("mfcc: num_ceps %d must be in [1, num_mel_bins = %d]" % (o["num_ceps"], o["num_mel_bins"]))
+    if _kind == "plp":
+        if not 1 <= o["lpc_order"] <= capi.PLP_MAX_LPC_ORDER:
+            raise ValueError("plp: lpc_order %d must be in [1, %d]" % (o["lpc_order"], capi.PLP_MAX_LPC_ORDER))
+        if not 1 <= o["num_ceps"] <= o["lpc_order"] + 1:
+            raise ValueError("plp: num_ceps %d must be in [1, lpc_order + 1 = %d]" % (o["num_ceps"], o["lpc_order"] + 1))
+        if not o["compress_factor"] > 0.0:
+            raise ValueError("plp: compress_factor %r must be positive" % (o["compress_factor"],))
+        if o["cepstral_scale"] == 0.0:
+            raise ValueError("plp: cepstral_scale 0 would zero every cepstrum (the C interface reads 0 as 'default 1')")
+    if o["return_raw_fft"]:
+        raise ValueError("spectrogram: return_raw_fft is not supported (the reference refuses it too)")
     if o["dither"] != 0.0:
         raise ValueError("fbank: dither is random noise and is not offered on the device path; set dither=0.0 (extraction configs do)")
     if o["window_type"] not in capi.WINDOW_TYPES:
@@ -66,11 +109,28 @@ def fbank_options(_kind="fbank", **kw):
     opts.cepstral_lifter = o["cepstral_lifter"]
     opts.blackman_coeff = o["blackman_coeff"]
     opts.vtln_warp, opts.vtln_low, opts.vtln_high = o["vtln_warp"], o["vtln_low"], o["vtln_high"]
+    opts.feature_kind = capi.FEATURE_KINDS[_kind]
+    opts.lpc_order, opts.compress_factor, opts.cepstral_scale = o["lpc_order"], o["compress_factor"], o["cepstral_scale"]
+    opts.return_raw_fft = int(o["return_raw_fft"])
     return opts, o
 
 
 def mfcc_options(**kw):
     return fbank_options("mfcc", **kw)
+
+
+def plp_options(**kw):
+    return fbank_options("plp", **kw)
+
+
+def spectrogram_options(**kw):
+    return fbank_options("spectrogram", **kw)
+
+
+def feature_dim(kind="fbank", **kw):
+    """Columns of a feature row of `kind` under the options `kw`: num_mel_bins + use_energy (fbank), num_ceps (mfcc, plp),
+    padded window / 2 + 1 (spectrogram) - what asv_fbank_dim answers for the same options block."""
+    return int(fbank_options(kind, **kw)[1]["dim"])
 
 
 def num_frames(num_samples, **kw):
@@ -93,7 +153,8 @@ def _frame_counts(lens, o):
 
 def fbank_device(wave, sample_off, mean_norm=False, std_norm=False, eps=1e-10, kind="fbank", **kw):
     """wave: 1-D f32 or int16 (16-bit PCM) CUDA tensor holding all utterances back to back, sample_off: int64 numpy [n+1].
-    Returns (feats [sum frames, dim] f32 CUDA tensor, frame_offsets int64 numpy [n+1]).  kind="mfcc": cepstra."""
+    Returns (feats [sum frames, dim] f32 CUDA tensor, frame_offsets int64 numpy [n+1]).  kind="mfcc" / "plp": cepstra,
+    "spectrogram": log power spectra."""
     import torch
     opts, o = fbank_options(kind, **kw)
     lib = capi.lib()
@@ -170,11 +231,12 @@ def de_silence_device(wave, sample_off, sample_rate, win_len=0.1, min_eng=50):
     return out[:int(out_off[-1])], out_off
 
 
-def fbank_packed(waveforms, device=None, de_silence=None, **kw):
+def fbank_packed(waveforms, device=None, de_silence=None, kind="fbank", **kw):
     """waveforms: list of 1-D float arrays / tensors (host or device), samples in the int16 value range.
     Returns (feats [sum frames, dim] f32 CUDA tensor, frame_offsets int64 numpy [n+1]) - the packed layout
     asv_net_extract consumes, so features never visit the host.  de_silence: {"win_len": seconds, "min_eng": threshold} trims the
-    (int16) waveforms on the device between the upload and the features (de_silence_device, at kw's sample_frequency); None: no trimming."""
+    (int16) waveforms on the device between the upload and the features (de_silence_device, at kw's sample_frequency); None: no trimming.
+    kind: "fbank", "mfcc", "plp" or "spectrogram" (fbank_options)."""
     import torch
     if len(waveforms) == 0:
         raise ValueError("fbank: empty batch")
@@ -199,7 +261,7 @@ def fbank_packed(waveforms, device=None, de_silence=None, **kw):
         if unknown:
             raise TypeError("fbank: unknown de_silence option(s) %s" % sorted(unknown))
         wave, sample_off = de_silence_device(wave, sample_off, kw.get("sample_frequency", _DEFAULTS["sample_frequency"]), **de_silence)
-    return fbank_device(wave, sample_off, **kw)
+    return fbank_device(wave, sample_off, kind=kind, **kw)
 
 
 def fbank(waveforms, **kw):
@@ -211,6 +273,16 @@ def fbank(waveforms, **kw):
 def mfcc(waveforms, **kw):
     """torchaudio.compliance.kaldi.mfcc for a batch: list of [frames, num_ceps] CUDA tensors."""
     return fbank(waveforms, kind="mfcc", **kw)
+
+
+def plp(waveforms, **kw):
+    """Kaldi PLP features (kaldifeat::Plp of the reference's runtime) for a batch: list of [frames, num_ceps] CUDA tensors."""
+    return fbank(waveforms, kind="plp", **kw)
+
+
+def spectrogram(waveforms, **kw):
+    """torchaudio.compliance.kaldi.spectrogram for a batch: list of [frames, padded window / 2 + 1] CUDA tensors, log energy in column 0."""
+    return fbank(waveforms, kind="spectrogram", **kw)
 
 
 def _off(a):

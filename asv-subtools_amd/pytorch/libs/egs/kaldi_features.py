@@ -31,7 +31,7 @@ class InputSequenceNormalization(object):
 
 class KaldiFeature(object):
     def __init__(self, feature_type='mfcc', kaldi_featset={}, mean_var_conf={}):
-        assert feature_type in ['mfcc', 'fbank']
+        assert feature_type in ['mfcc', 'fbank', 'plp', 'spectrogram']      # the four of the reference's makeFeatures.sh
         self.feat_type = feature_type
         self.kaldi_featset = dict(kaldi_featset)
         self.mean_var_conf = dict(mean_var_conf)

@@ -8,7 +8,9 @@ pipeline/extract_xvectors_for_pytorch_new.sh):
                                  [--use-gpu true] [--gpu-id N] model-path wav.scp vectors-wspecifier
 
 wav.scp holds "utt-id path.wav" lines (reference libs/support/utils.py:625-638); feat.yaml holds the reference's
-feature_extraction_conf: {feature_type: fbank|mfcc, kaldi_featset: {...torchaudio names...}, mean_var_conf: {...}}.
+feature_extraction_conf: {feature_type: fbank|mfcc|plp|spectrogram, kaldi_featset: {...torchaudio names...}, mean_var_conf: {...}}
+(the four feature types of the reference's makeFeatures.sh; plp adds lpc_order / compress_factor / cepstral_scale).  The width the
+options give must be the model's inputs_dim: anything else is a ValueError naming both numbers, before the first launch.
 
 Where the reference decodes, computes torchaudio features, uploads and embeds one utterance at a time (lines 118-135),
 this script ships 16-bit PCM (half the bytes of float features), and runs front-end + extractor on the device per batch:
@@ -100,15 +102,29 @@ def device_desilence():
     return os.environ.get("ASV_AMD_DEVICE_DESILENCE", "1") != "0"
 
 
+def check_feature_width(model, kind, featset, sample_frequency=None):
+    """ValueError unless features of `kind` under `featset` are as wide as the model's input (no launch involved)."""
+    from libs.amd import engine as amd_engine, ir
+    kw = dict(featset) if sample_frequency is None else dict(featset, sample_frequency=float(sample_frequency))
+    try:
+        want = amd_engine.infer_feat_dim(model)
+    except ir.TraceError:
+        return                                                       # a model that does not say: the engine compares per batch
+    width = frontend.feature_dim(kind, **kw)
+    if width != want:
+        raise ValueError("feat-config gives %s features of width %d, but the model's inputs_dim is %d" % (kind, width, want))
+
+
 def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, batch_utts=512, num_readers=4, amp_th=None):
     """items: [(key, wav path)].  amp_th: the de-silence threshold, None: no trimming.  Returns (number written, device seconds, audio
     seconds as frames * 0.01 like the reference)."""
     import queue
     import threading
     from concurrent.futures import ThreadPoolExecutor
-    engine = model._amd_engine()
     kind = feat_conf.get("feature_type", "mfcc")
     featset = dict(feat_conf.get("kaldi_featset", {}) or {})
+    check_feature_width(model, kind, featset)                        # before the engine exists: nothing has touched the device yet
+    engine = model._amd_engine()
     mv = feat_conf.get("mean_var_conf", {})
     mean_norm = bool(mv.get("mean_norm", True)) if mv is not None else False      # processor.py:410-413: {} -> defaults, None -> identity
     std_norm = bool(mv.get("std_norm", False)) if mv is not None else False
@@ -177,6 +193,7 @@ def extract_wavs(model, items, w, feat_conf, max_chunk, batch_seconds=1200.0, ba
             wave_dev = host[:int(off[-1])].to(dev, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()             # the upload has read the pinned buffer: hand it back
             free_bufs.put(host)
+            check_feature_width(model, kind, featset, sr)            # (the spectrogram's width follows the files' sample rate)
             e0.record()
             if trim_device:
                 wave_dev, off = frontend.de_silence_device(wave_dev, off, sr, min_eng=amp_th)

@@ -613,7 +613,8 @@ int asv_class_scatter_f64(const float *x, int ldx, int n_rows, int dim, const in
                           double *sum_out, double *xtx_out, double *class_scatter_out, void *stream);
 
 /* ---- acoustic front-end -------------------------------------------
- * Kaldi-compatible log-mel filterbank features of packed waveforms on the device: what
+ * Kaldi-compatible features of packed waveforms on the device - log-mel filterbank, MFCC, PLP and spectrogram, the four feature
+ * types of the reference's makeFeatures.sh (runtime/kaldifeat/csrc/feature-{fbank,mfcc,plp,spectrogram}.cc).  Filterbank: what
  * torchaudio.compliance.kaldi.fbank computes in pytorch/libs/egs/kaldi_features.py:72-137 and kaldifeat::Fbank in
  * runtime/kaldifeat/csrc/feature-fbank.cc (the field names and defaults below are FbankOptions / FrameExtractionOptions /
  * MelBanksOptions of that code).  Samples are floats in the int16 value range (Kaldi WaveData); dither is not offered
@@ -651,11 +652,37 @@ typedef struct asv_fbank_opts {
   float   blackman_coeff;       /* 0.42 (ASV_WINDOW_BLACKMAN, feature-window.cc:47-49)                                   */
   float   vtln_warp;            /* 1: none.  VTLN warping of the mel bin edges (mel-computations.cc:20-89, 129-161)      */
   float   vtln_low, vtln_high;  /* 100 / -500 (negative: offset from Nyquist): the cut-offs of the piecewise-linear warp */
+  /* ---- fields behind ASV_FBANK_OPTS_SIZE_V1: a caller that passes that struct_size gets feature_kind 0 ----
+   * ASV_FEAT_SPECTROGRAM (feature-spectrogram.cc:22-64): log(max(|X_k|^2, FLT_EPSILON)) of bins 0 .. padded / 2, the Nyquist
+   *   bin included; column 0 is always the log energy (raw_energy: before / after pre-emphasis and window), floored at
+   *   log(energy_floor).  The mel, cepstral, use_energy and htk_compat fields are ignored.
+   * ASV_FEAT_PLP (feature-plp.cc:80-183, mel-computations.cc:214-349): power-spectrum mel energies (num_bins, low_freq,
+   *   high_freq, the VTLN fields) x equal loudness -> pow(compress_factor) -> first and last value doubled -> IDFT to
+   *   lpc_order + 1 autocorrelations -> Durbin's recursion -> LPC to cepstrum; num_ceps columns: C0 = -log(1 / E) (floored at
+   *   FLT_EPSILON like the reference), then the first num_ceps - 1 cepstra; liftered (cepstral_lifter 0: no lifter), times
+   *   cepstral_scale; with use_energy column 0 is the log energy; htk_compat moves column 0 last (no sqrt 2 factor).
+   *   num_ceps 0 means 13, lpc_order 0 means 12, compress_factor 0 means 0.33333, cepstral_scale 0 means 1 (a zero-filled
+   *   tail asks for the reference's defaults); 1 <= lpc_order <= ASV_PLP_MAX_LPC_ORDER, num_ceps <= lpc_order + 1,
+   *   compress_factor > 0.  The recursion and the cepstrum run in the reference's statement order, one lane per frame. */
+  int32_t feature_kind;         /* ASV_FEAT_FBANK: filterbank or (num_ceps > 0) MFCC output, as before */
+  int32_t lpc_order;            /* 12    */
+  float   compress_factor;      /* 0.33333 */
+  float   cepstral_scale;       /* 1     */
+  int32_t return_raw_fft;       /* 0; anything else is refused, as the reference refuses it */
 } asv_fbank_opts_t;
+#define ASV_FEAT_FBANK         0
+#define ASV_FEAT_SPECTROGRAM   1
+#define ASV_FEAT_PLP           2
+#define ASV_PLP_MAX_LPC_ORDER  63
+/* struct_size of the options block before feature_kind was appended (= offsetof(asv_fbank_opts_t, feature_kind)) */
+#define ASV_FBANK_OPTS_SIZE_V1 96u
 /* Frames an utterance of num_samples yields (feature-window.cc:71-114); -1 on bad options. */
 long long asv_fbank_num_frames(const asv_fbank_opts_t *opts, long long num_samples);
+/* Columns of a feature row: num_bins + use_energy (filterbank), num_ceps (MFCC, PLP), padded / 2 + 1 (spectrogram; padded =
+ * the window rounded up to a power of two); -1 on options asv_fbank would refuse for their sizes. */
+int asv_fbank_dim(const asv_fbank_opts_t *opts);
 /* wave: device floats, utterance u = samples [sample_offsets[u], sample_offsets[u+1]) (host int64 [n_utts+1]);
- * feats: device [sum of frames][dim] f32, utterances back to back in order; dim = num_bins + use_energy, or num_ceps. */
+ * feats: device [sum of frames][dim] f32, utterances back to back in order; dim = asv_fbank_dim(opts). */
 int asv_fbank(const asv_fbank_opts_t *opts, const float *wave, const long long *sample_offsets, int n_utts,
               float *feats, void *stream);
 /* The same with 16-bit PCM samples in HBM (half the ingest; SURVEY.md 8(f) rank 2 "ship int16 PCM"). */
