@@ -83,6 +83,16 @@ __device__ __forceinline__ f32x16_t mfma16(const uint4 a, const uint4 b, const f
   else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
 
+// the narrow shape of the same instruction: D = A (16 x 32) . B (32 x 16) + C, f32 accumulate; half the output tile at twice the K,
+// so two of these do the work of one mfma16 in the same matrix-pipe cycles (16 against 32).  Lane l holds row l & 15 of A (column
+// l & 15 of B) and the k-octet l >> 4 (k = 8 (l >> 4) + e, e = 0..7) in its 16 bytes; D has col = l & 15, row = 4 (l >> 4) + reg.
+template <int ET>
+__device__ __forceinline__ f32x4_t mfma16n(const uint4 a, const uint4 b, const f32x4_t c) {
+  static_assert(ET == ET_BF16 || ET == ET_F16, "16-bit element types only");
+  if constexpr (ET == ET_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+}
+
 // ReLU of a packed pair of 16-bit floats as ONE integer instruction (v_pk_max_i16 x, 0): a negative float of either format has
 // its sign bit set = a negative int16, non-negative ones are unchanged (-0 -> +0; a NaN with the sign bit becomes 0)
 __device__ __forceinline__ uint32_t relu_h16x2(uint32_t w) {

@@ -48,6 +48,28 @@
 // the datasheet rate on trivial operands (the loads alone 87 %, the LDS reads alone 76 %, no fetches 98 %); these loops run at ~67 % in wall-clock
 // terms.  0.75 fetches per matrix instruction is what 128 accumulator registers per wave allow whatever the wave's tile shape; more frames
 // per resident tile would cut the loads (128 x 512 x 16 bit IS the LDS).
+// The other matrix-instruction shape (template arguments NY / NL, mfma16n in device_utils.h): every K loop also exists on v_mfma_f32_16x16x32 -
+// the same 128 x 64 wave tile as 8 x 4 accumulators of 4 registers, the same wfrag order (a narrow weight fragment is a 16-byte gather of four
+// 256-byte runs from it), the same Y image, ring, swizzles, barriers and fetch distances, the same operand bytes per K; the last layer's pooling
+// epilogue then walks 16-frame fragments and merges lane groups l and l ^ 32 about a common pivot before it publishes a half.  The bare probe
+// with this kernel's mix on RANDOM bf16 (tools/vmem_probe.hip `shape`, profiles/chain_mfma_shape_probe.txt): 32x32x16 1239 - 1345 s_memtime
+// ticks per 128 x 64 x 32 step of both waves of a SIMD (1024 = the matrix pipe's), 16x16x32 989 - 1100: 782 - 838 ns against 677 - 731 ns per
+// step at the SAME clock (1.68 - 1.78 GHz once warm; 2.3 - 2.4 GHz and the same ratio on zeros).  So the narrow shape's gain is in the issue
+// stream - a fetch between two 16-cycle instructions costs the wave's matrix stream less than one between two 32-cycle ones - not in the
+// clock.  Results: the Y-writing phases are BIT-identical on both shapes (one 16x16x32 sums its 32 products in the order of two 32x32x16);
+// the narrow last layer differs from the wide one by the order of the pooled sums (2e-6 of the embedding).
+// In the kernel (256 x 200 frames, stamps of one session, profiles/chain_mfma_shape_stamps.txt; ticks per tile, wide -> narrow): layer A's loop
+// 61.4 k -> 54.2 k, the middle layer's 20.8 k -> 17.2 k (16.4 k = the pipe's) at the same 1.94 GHz, 89.5 -> 82.9 us per workgroup; the last layer's
+// three loops 21.0 / 14.9 / 13.4 k -> 20.5 / 15.0 / 13.9 k with its epilogues 9.0 / 10.7 / 7.0 k -> 12.1 / 13.7 / 11.1 k at 2.03 GHz: the 16-frame
+// run walk costs more than its loops save.  By wall clock (profiles/chain_mfma_shape_ab.txt, one box, alternating): in one process NY 332.5 ->
+// 322.1 us per step, NL 333.6, both 330.4; kernel 187.9 -> 178.2 us (rocprofv3, StdDev 3.4 - 3.9); bench --full 926.7 - 939.3 k -> 967.0 - 978.5 k
+// utterances/s (no overlap), the plain 20-step figure 769.9 - 792.0 k -> 791.1 - 820.3 k (overlaps by 0.1 %).  SHIPPED: NY = 1, NL = 0.
+// Resources (-Rpass-analysis=kernel-resource-usage, bf16 = f16; 128- / 96- / 64-frame form): wide 256 VGPRs + 12 B scratch / 216 / 162; NY 256 + 28 B /
+// 226 / 166; NL 256 + 16 B / 214 / 160; both 256 + 28 B / 226 / 166; no AGPRs.  The scratch slots of the 128-frame forms (three dwords before this
+// change, seven with NY) hold loop-invariant addresses, stored in the prologue and re-read between the phases - in the assembly of the NY form
+// none is touched inside a K loop.  LDS bank conflicts (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE per dispatch, a counter run of its own,
+// profiles/chain_mfma_shape_lds_conflicts.txt): wide 0.87 M / 13.8 M, NY 4.30 M / 17.3 M - the narrow operand's ds_read_b128 row read is the 2-way case on
+// the ring and on Y, a quarter of its LDS cycles; it won all the same.  Open: a swizzle that serves the 16-row read without conflicts.
 // One workgroup (512 threads, 160 KiB LDS) per CU.
 #include <cstdlib>
 
@@ -92,14 +114,20 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 //        4 (results valid) = the last layer in lockstep: a workgroup barrier behind every unit's K loop and behind every pooling
 //        epilogue, so that the two waves of a SIMD run their loops together (sharing the matrix pipe at its full rate) and their
 //        epilogues together (no matrix stream beside the packed f32 arithmetic, which otherwise only issues in its gaps).
-template <int POOLV, int ET = ET_BF16, int ABL = 0, int MF = 4>
+// NY / NL: the matrix instruction of the Y-writing phases (layer A, middle layers) / of the last layer: 0 = 32x32x16 (mfma16), 1 = 16x16x32
+//        (mfma16n) on the same 128 x 64 wave tile - 8 x 4 accumulators of 4 registers instead of 4 x 2 of 16 - from the same wfrag order, the same
+//        Y image and window ring.  The product instantiates one value per phase (kChainNarrowY / kChainNarrowL); the other lives in the
+//        developer build (ASV_AMD_CHAIN_MFMA).
+template <int POOLV, int ET = ET_BF16, int ABL = 0, int MF = 4, int NY = 0, int NL = 0>
 __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParams p) {
   using Geo = ChainGeom<MF>;
+  static_assert(!NL || (POOLV == 1 && (ABL == 0 || ABL == 3)), "the narrow last layer has the run-based pooling epilogue only");
   constexpr int CM = Geo::CM, CSTAGE = Geo::CSTAGE, CGROUPS = Geo::CGROUPS, CPIECES = Geo::CPIECES, SCR_OFF = Geo::SCR_OFF;
   __shared__ __attribute__((aligned(16))) unsigned char lds[Geo::LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // 0..7: channel slice of phases 1-2, unit index of the last
   const int lr = lane & 31, lh = lane >> 5;
+  const int lc = lane & 15, lo = lane >> 4;                         // the narrow shape's lane = (row or column lc, k-octet lo)
   const int m0 = p.row_base + blockIdx.x * CM;                      // (row_base / tile_base: the launch's first row and tile, launch_tdnn_chain)
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte *)lds);
   float *par = reinterpret_cast<float *>(lds + SCR_OFF);            // bias[512] | scale[512] | shift[512] of the layer in flight
@@ -156,6 +184,36 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
     }
   };
 
+  // The narrow shape (mfma16n: A = 16 channels x 32 k, B = 32 k x 16 frames).  A weight fragment is a per-lane 16-byte gather from the
+  // wfrag order [n_frag32][tap][chunk64][k_group16][lane = (lh, lr)][8]: lane (lc, lo) of channel half h of 32-k step kg2 reads k-group
+  // 2 kg2 + (lo >> 1) at lane slot (lo & 1) * 32 + 16 h + lc - four 256-byte runs over the cache lines of the wide shape's two 1 KiB runs.
+  // wn[kg2][cf]: channel fragment cf = 2 j + h of the wave's 64; accn[f][cf][e] = frame 16 f + lc, channel 16 cf + 4 lo + e.
+  uint4 wn[2][4];
+  f32x4_t accn[2 * MF][4];
+  struct XFragsN { uint4 x[2 * MF]; };
+  const uint32_t lane16n = (uint32_t)((lo >> 1) * 1024 + ((lo & 1) * 32 + lc) * 16);
+  auto load_wn = [&](const unsigned char *w0, const unsigned char *w1, size_t at, int kg2, int cf) {
+    wn[kg2][cf] = *reinterpret_cast<const uint4 *>(((cf >> 1) ? w1 : w0) + at + (size_t)(kg2 * 2048 + (cf & 1) * 256) + lane16n);
+  };
+  auto init_acc_n = [&](const float *bias64) {
+#pragma unroll
+    for (int cf = 0; cf < 4; ++cf) {
+      const float4 b4 = *reinterpret_cast<const float4 *>(bias64 + 16 * cf + 4 * lo);
+#pragma unroll
+      for (int f = 0; f < 2 * MF; ++f) { accn[f][cf][0] = b4.x; accn[f][cf][1] = b4.y; accn[f][cf][2] = b4.z; accn[f][cf][3] = b4.w; }
+    }
+  };
+  // one step of a narrow k-group: channel fragment s / 2 against one half of the frame fragments (the wide loop's order: a weight fragment is
+  // dead after its second step and is re-fetched there for the next chunk - the same fetch distance)
+  // TR = false: D = W X^T as above; TR = true: D = X W^T - accn[f][cf][e] = CHANNEL 16 cf + lc, frame 16 f + 4 lo + e (the pooling epilogue's)
+  auto mma_n = [&](const XFragsN &f, int kg2, int s, auto tr) {
+#pragma unroll
+    for (int i = (s & 1) * MF; i < (s & 1) * MF + MF; ++i) {
+      if constexpr (decltype(tr)::value) accn[i][s >> 1] = mfma16n<ET>(f.x[i], wn[kg2][s >> 1], accn[i][s >> 1]);
+      else accn[i][s >> 1] = mfma16n<ET>(wn[kg2][s >> 1], f.x[i], accn[i][s >> 1]);
+    }
+  };
+
   // ================================ phase 1: layer A through the window ring ================================
   stage_params(p.first);
   {
@@ -197,11 +255,26 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
     auto load_x4 = [&](uint32_t xb, int kg, int i, XFrags &f) {
       f.x[i] = *reinterpret_cast<const uint4 *>(lds + (xb ^ (uint32_t)(kg << 5)) + i * 4096);
     };
+    // narrow: window row lc + 16 f (+ halo + tap), octet 4 kg2 + lo - the swizzle term is blind to +16 rows too, kg2 enters as an XOR of bit 6
+    auto x_base_n = [&](int c, int d) -> uint32_t {
+      const int wrow = lc + kHalo + d;
+      return (uint32_t)((c % CSTAGES) * CSTAGE + wrow * CROWB + ((lo ^ ((wrow >> 1) & 7)) << 4));
+    };
+    auto load_xn = [&](uint32_t xb, int kg2, int f, XFragsN &fr) {
+      fr.x[f] = *reinterpret_cast<const uint4 *>(lds + (xb ^ (uint32_t)(kg2 << 6)) + f * 2048);
+    };
     issue_A(0, 0);
+    if constexpr (NY) {
 #pragma unroll
-    for (int kg = 0; kg < 4; ++kg) {
-      wf[kg][0] = *reinterpret_cast<const uint4 *>(wA0 + (size_t)kg * 1024 + lane16);
-      wf[kg][1] = *reinterpret_cast<const uint4 *>(wA1 + (size_t)kg * 1024 + lane16);
+      for (int kg2 = 0; kg2 < 2; ++kg2)
+#pragma unroll
+        for (int cf = 0; cf < 4; ++cf) load_wn(wA0, wA1, 0, kg2, cf);
+    } else {
+#pragma unroll
+      for (int kg = 0; kg < 4; ++kg) {
+        wf[kg][0] = *reinterpret_cast<const uint4 *>(wA0 + (size_t)kg * 1024 + lane16);
+        wf[kg][1] = *reinterpret_cast<const uint4 *>(wA1 + (size_t)kg * 1024 + lane16);
+      }
     }
     if (nchunks > 2) {
       issue_A(1, 1);
@@ -214,9 +287,48 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stamp();                                                     // 1: first window + fragments in
-    init_acc(p.first.bias + wave * 64);
     const int v_taps = p.taps[lane < 9 ? lane : 0];
     const int d_first = __builtin_amdgcn_readlane(v_taps, 0);
+    if constexpr (NY) {
+      init_acc_n(p.first.bias + wave * 64);
+      XFragsN y0, y1;
+      uint32_t xb = x_base_n(0, d_first);
+#pragma unroll
+      for (int f = 0; f < 2 * MF; ++f) load_xn(xb, 0, f, y0);
+#pragma unroll 1
+      for (int c = 0; c < nchunks; ++c) {
+        for (int t = 0; t < n_taps; ++t) {
+          const bool last_tap = (t + 1 == n_taps);
+          int cn = c, tn = t + 1;
+          if (last_tap) { tn = 0; cn = c + 1; }
+          const bool more = cn < nchunks;
+          if (!more) { cn = c; tn = t; }                     // the last step re-fetches its own fragments (never used)
+          const size_t wnext = ((size_t)tn * nchunks + cn) * 4096;
+          auto group = [&](const XFragsN &xc, int kg2, XFragsN &xn, uint32_t xbn, int kg2n) {
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+              if (s < 2 * MF) load_xn(xbn, kg2n, s, xn);
+              mma_n(xc, kg2, s, TrNo{});
+              if (s & 1) load_wn(wA0, wA1, wnext, kg2, s >> 1);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          };
+          group(y0, 0, y1, xb, 1);
+          if (last_tap && c + 1 < nchunks) {
+            // the youngest 4 VMEM operations are this step's fragment fetches; the pieces of window c + 2 may still be in flight behind window
+            // c + 1 (in the first step nothing else lies between them: hence not the wide loop's 8)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + CPIECES) : "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            if (c + 3 < nchunks) issue_A(c + 3, (c + 3) % CSTAGES);
+          }
+          const uint32_t xbn = x_base_n(cn, __builtin_amdgcn_readlane(v_taps, tn));
+          group(y1, 1, y0, xbn, 0);
+          xb = xbn;
+        }
+      }
+    } else {
+    init_acc(p.first.bias + wave * 64);
     XFrags x0, x1;
     uint32_t xb = x_base(0, d_first);
 #pragma unroll
@@ -254,6 +366,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
         group(x1, 3, x0, xbn, 0);
         xb = xbn;
       }
+    }
     }
   }
 
@@ -304,6 +417,87 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
           *reinterpret_cast<uint2 *>(dst + i * 32 * YROWB) = pk;
         }
       }
+  };
+
+  // the same from the narrow shape's accumulators: accn[f][cf][0..3] = channels wave * 64 + 16 cf + 4 lo + 0..3 of frame 16 f + lc - the 8 bytes at
+  // half lo & 1 of the 16-byte slot wave * 8 + 2 cf + (lo >> 1) of row 16 f + lc (whose swizzle is lc)
+  auto store_Y_n = [&](int relu, bool affine) {
+    const float act_lo = relu ? 0.0f : -INFINITY;
+    unsigned char *yrow = lds + lc * YROWB + (lo & 1) * 8;
+    auto body = [&](auto aff) {
+    constexpr bool affine = decltype(aff)::value;
+#pragma unroll
+    for (int cf = 0; cf < 4; ++cf) {
+      unsigned char *dst = yrow + (((wave * 8 + cf * 2 + (lo >> 1)) ^ lc) << 4);
+      float sc[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (affine) {
+        const int chl = wave * 64 + 16 * cf + 4 * lo;
+        const float4 sc4 = *reinterpret_cast<const float4 *>(par + CN + chl);
+        const float4 sh4 = *reinterpret_cast<const float4 *>(par + 2 * CN + chl);
+        sc[0] = sc4.x; sc[1] = sc4.y; sc[2] = sc4.z; sc[3] = sc4.w;
+        sh[0] = sh4.x; sh[1] = sh4.y; sh[2] = sh4.z; sh[3] = sh4.w;
+      }
+#pragma unroll
+      for (int f = 0; f < 2 * MF; ++f) {
+        uint2 pk;
+        if constexpr (affine) {
+          float y[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) y[e] = fmaf(max_lo(accn[f][cf][e], act_lo), sc[e], sh[e]);
+          pk.x = pack_h16x2<ET>(y[0], y[1]);
+          pk.y = pack_h16x2<ET>(y[2], y[3]);
+        } else {
+          pk.x = pack_h16x2<ET>(accn[f][cf][0], accn[f][cf][1]);
+          pk.y = pack_h16x2<ET>(accn[f][cf][2], accn[f][cf][3]);
+          if (relu) { pk.x = relu_h16x2(pk.x); pk.y = relu_h16x2(pk.y); }
+        }
+        *reinterpret_cast<uint2 *>(dst + f * 16 * YROWB) = pk;
+      }
+    }
+    };
+    if (affine) body(TrYes{}); else body(TrNo{});
+  };
+
+  // the Y-fed main loop on the narrow shape: 8 chunks of 2 k-groups of 32; Y row 16 f + lc, octet chunk * 8 + 4 kg2 + lo
+  auto yloop_n = [&](const unsigned char *wb0, const unsigned char *wb1, const float *bias64, auto tr) {
+    const uint32_t yb = (uint32_t)(lc * YROWB);
+    const uint32_t sx = (uint32_t)(lo ^ lc);
+    auto load_yn = [&](int c, int kg2, int f, XFragsN &fr) {     // slot (c*8 + kg2*4 + lo) ^ lc = (c*8 + kg2*4) ^ sx
+      fr.x[f] = *reinterpret_cast<const uint4 *>(lds + yb + ((((uint32_t)(c * 8 + kg2 * 4)) ^ sx) << 4) + f * 16 * YROWB);
+    };
+#pragma unroll
+    for (int kg2 = 0; kg2 < 2; ++kg2)
+#pragma unroll
+      for (int cf = 0; cf < 4; ++cf) load_wn(wb0, wb1, 0, kg2, cf);
+    if constexpr (decltype(tr)::value) {                        // lane = channel: one bias per lane and channel fragment
+#pragma unroll
+      for (int cf = 0; cf < 4; ++cf) {
+        const float b = bias64[16 * cf + lc];
+#pragma unroll
+        for (int f = 0; f < 2 * MF; ++f) { accn[f][cf][0] = b; accn[f][cf][1] = b; accn[f][cf][2] = b; accn[f][cf][3] = b; }
+      }
+    } else {
+      init_acc_n(bias64);
+    }
+    XFragsN y0, y1;
+#pragma unroll
+    for (int f = 0; f < 2 * MF; ++f) load_yn(0, 0, f, y0);
+#pragma unroll 1
+    for (int c = 0; c < CN / CBK; ++c) {
+      const int cn = min(c + 1, CN / CBK - 1);
+      const size_t wnext = (size_t)cn * 4096;
+      auto group = [&](const XFragsN &xc, int kg2, XFragsN &xn, int c2, int kg2n) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          if (s < 2 * MF) load_yn(c2, kg2n, s, xn);
+          mma_n(xc, kg2, s, tr);
+          if (s & 1) load_wn(wb0, wb1, wnext, kg2, s >> 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      group(y0, 0, y1, c, 1);
+      group(y1, 1, y0, cn, 0);
+    }
   };
 
   // main loop of a layer whose input is Y: K = 512 = 8 steps of 4 k-groups, fragments of the next step prefetched, no barrier.
@@ -358,7 +552,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
   __builtin_amdgcn_s_barrier();            // every wave is done with the ring: Y may be written
   asm volatile("" ::: "memory");
   stamp();                                 // 3
-  store_Y(p.first.relu, p.first.scale != nullptr);
+  if constexpr (NY) store_Y_n(p.first.relu, p.first.scale != nullptr); else store_Y(p.first.relu, p.first.scale != nullptr);
   __builtin_amdgcn_s_barrier();            // Y complete; the constants of layer A are dead
   asm volatile("" ::: "memory");
   stamp();                                 // 4: Y of layer A complete
@@ -370,12 +564,12 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
     stage_params(L);
     const size_t frag_stride = (size_t)(CN / CBK) * 4096;
     const unsigned char *wb = reinterpret_cast<const unsigned char *>(L.wfrag) + (size_t)(wave * 2) * frag_stride;
-    yloop(wb, wb + frag_stride, L.bias + wave * 64, TrNo{});
+    if constexpr (NY) yloop_n(wb, wb + frag_stride, L.bias + wave * 64, TrNo{}); else yloop(wb, wb + frag_stride, L.bias + wave * 64, TrNo{});
     stamp();                               // 5: main loop of the middle layer done
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();          // nobody reads the old Y any more (and the staged constants are visible)
     asm volatile("" ::: "memory");
-    store_Y(L.relu, L.scale != nullptr);
+    if constexpr (NY) store_Y_n(L.relu, L.scale != nullptr); else store_Y(L.relu, L.scale != nullptr);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stamp();                               // 6: Y of the middle layer complete
@@ -394,7 +588,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
 #pragma unroll 1
     for (int cb = wave * 64; cb < L.cout_pad; cb += 512) {
       const unsigned char *wb = reinterpret_cast<const unsigned char *>(L.wfrag) + (size_t)(cb / 32) * frag_stride;
-      yloop(wb, wb + frag_stride, L.bias + cb, TrYes{});
+      if constexpr (NL) yloop_n(wb, wb + frag_stride, L.bias + cb, TrYes{}); else yloop(wb, wb + frag_stride, L.bias + cb, TrYes{});
       if constexpr (ABL == 4) __builtin_amdgcn_s_barrier();
       stamp();                             // 7, 9, 11: main loop of a unit done
       // Pooling epilogue, registers only.  acc[i][j][r] = channel cb + j*32 + lr, frame i*32 + 8 (r >> 2) + 4 lh + (r & 3): a
@@ -413,7 +607,100 @@ __global__ __launch_bounds__(512, 2) void tdnn_chain_kernel(const TdnnChainParam
         continue;
       }
       const float sc[2] = {(ABL != 2 && L.scale != nullptr) ? L.scale[cb + lr] : 1.0f, (ABL != 2 && L.scale != nullptr) ? L.scale[cb + 32 + lr] : 1.0f};
-      if constexpr (POOLV == 0) {
+      if constexpr (NL) {
+        // The narrow shape: accn[f][cf][e] = channel cb + 16 cf + lc, frame 16 f + 4 lo + e.  Bit 2 of a frame is lo & 1, so lane groups lo and
+        // lo ^ 2 (lanes l and l ^ 32) hold the frames of ONE published half: they sum about a COMMON pivot - the first frame of the utterance
+        // that either of them holds, in whichever fragment of the tile it lies (the pivot rule of chain_pool.h), exchanged across l ^ 32 when it
+        // is taken - so their sums add directly at publication; the lower group (lo < 2) writes.  The run walk is per 16-frame fragment.
+        float ps[4] = {0.f, 0.f, 0.f, 0.f}, pq[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
+        float scn[4];
+#pragma unroll
+        for (int cf = 0; cf < 4; ++cf) scn[cf] = L.scale != nullptr ? L.scale[cb + 16 * cf + lc] : 1.0f;
+        const bool first_unit = ABL == 3 && cb < 512;
+        if (first_unit) fine(0);
+        int cur_seg = -1;                    // uniform: all lanes walk the utterances of the tile together
+        bool have = false;                   // per lane pair: pv is a frame of cur_seg
+        auto publish = [&]() {
+          if (cur_seg < 0) return;
+          float ts[4], tq[4];
+#pragma unroll
+          for (int cf = 0; cf < 4; ++cf) { ts[cf] = ps[cf] + __shfl_xor(ps[cf], 32); tq[cf] = pq[cf] + __shfl_xor(pq[cf], 32); }
+          if (lo < 2) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {      // channels cb + (16 h + lc) and cb + 32 + (16 h + lc): fragments h and 2 + h
+              const float a[2] = {ts[h], ts[2 + h]}, b[2] = {tq[h], tq[2 + h]}, c[2] = {pv[h], pv[2 + h]}, d[2] = {scn[h], scn[2 + h]};
+              pool_publish_moments(p, half, first_seg, cur_seg, cb, 16 * h + lc, lo, a, b, c, d);
+            }
+          }
+        };
+#pragma unroll
+        for (int f = 0; f < 2 * MF; ++f) {
+          const int rs_vec = (f < 4) ? rowseg_lo : rowseg_hi;
+          const int shift = (f & 3) * 16;
+          uint32_t rem = (uint32_t)(__builtin_amdgcn_ballot_w64(rs_vec >= 0) >> shift) & 0xffffu;
+          if (rem != 0) {
+            float u[4][4];
+#pragma unroll
+            for (int cf = 0; cf < 4; ++cf)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) u[cf][e] = max_lo(accn[f][cf][e], act_lo);
+            while (rem != 0) {                 // one run per utterance present, in row order
+              const int sg = __builtin_amdgcn_readlane(rs_vec, shift + __builtin_ctz(rem));
+              const uint32_t bits = (uint32_t)(__builtin_amdgcn_ballot_w64(rs_vec == sg) >> shift) & rem;
+              rem &= ~bits;
+              if (sg != cur_seg) {
+                publish();
+                cur_seg = sg;
+                have = false;
+#pragma unroll
+                for (int cf = 0; cf < 4; ++cf) { ps[cf] = 0.0f; pq[cf] = 0.0f; }
+              }
+              // register e of this lane holds frame 4 lo + e -> bit e of the lane's mask; lmp: the partner's (lane l ^ 32)
+              const uint32_t lm = (bits >> (4 * lo)) & 0xfu, lmp = (bits >> (4 * (lo ^ 2))) & 0xfu;
+              const bool need = !have && (lm | lmp) != 0;
+              if (__builtin_amdgcn_ballot_w64(need) != 0) {
+                const int rsel = lm != 0 ? __builtin_ctz(lm) : 0;
+                const bool own = (lo < 2) ? lm != 0 : lmp == 0;            // the pair's first frame lies in the lower group if that has one
+#pragma unroll
+                for (int cf = 0; cf < 4; ++cf) {
+                  float c = u[cf][0];
+#pragma unroll
+                  for (int e = 1; e < 4; ++e) c = (rsel == e) ? u[cf][e] : c;
+                  const float o = __shfl_xor(c, 32);
+                  pv[cf] = need ? (own ? c : o) : pv[cf];
+                }
+                have = have || need;
+              }
+              if (bits == 0xffffu) {
+                // the whole fragment is one utterance: packed f32, no masks
+#pragma unroll
+                for (int cf = 0; cf < 4; ++cf) {
+                  const f32x2_t pv2 = {pv[cf], pv[cf]};
+                  const f32x2_t d0 = (f32x2_t){u[cf][0], u[cf][1]} - pv2, d1 = (f32x2_t){u[cf][2], u[cf][3]} - pv2;
+                  const f32x2_t st = d0 + d1, qt = __builtin_elementwise_fma(d1, d1, d0 * d0);
+                  ps[cf] += st.x + st.y;
+                  pq[cf] += qt.x + qt.y;
+                }
+              } else {
+                const int t0 = (int)(lm << 31) >> 31, t1 = (int)(lm << 30) >> 31, t2 = (int)(lm << 29) >> 31, t3 = (int)(lm << 28) >> 31;   // all ones where the frame is in the run
+#pragma unroll
+                for (int cf = 0; cf < 4; ++cf) {
+                  const f32x2_t pv2 = {pv[cf], pv[cf]};
+                  f32x2_t d0 = (f32x2_t){u[cf][0], u[cf][1]} - pv2, d1 = (f32x2_t){u[cf][2], u[cf][3]} - pv2;
+                  d0.x = __int_as_float(__float_as_int(d0.x) & t0); d0.y = __int_as_float(__float_as_int(d0.y) & t1);
+                  d1.x = __int_as_float(__float_as_int(d1.x) & t2); d1.y = __int_as_float(__float_as_int(d1.y) & t3);
+                  const f32x2_t st = d0 + d1, qt = __builtin_elementwise_fma(d1, d1, d0 * d0);
+                  ps[cf] += st.x + st.y;
+                  pq[cf] += qt.x + qt.y;
+                }
+              }
+            }
+          }
+          if (first_unit && (f & 1)) fine(1 + f / 2);
+        }
+        publish();
+        if (first_unit) fine(5);
+      } else if constexpr (POOLV == 0) {
         float ps[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f}, pv[2] = {0.f, 0.f};
         int cur_seg = -1;                    // per lane: the halves cross an utterance seam at different registers
         auto publish = [&](bool mine) {      // lanes with `mine` write the moments of their current segment
@@ -605,6 +892,38 @@ ChainTilePlan chain_tile_plan(int rows, bool allow_tail) {
   return plan;
 }
 
+// Which matrix-instruction shape each phase ships with (1 = 16x16x32): decided by wall clock on alternating runs of the flagship step,
+// profiles/chain_mfma_shape_ab.txt.  The other instantiations exist in the developer build only (ASV_AMD_CHAIN_MFMA below).
+#ifndef CHAIN_MFMA_SHAPES
+#define CHAIN_MFMA_SHAPES 1  // experiment builds: bit 0 = the Y-writing phases, bit 1 = the last layer
+#endif
+constexpr int kChainNarrowY = CHAIN_MFMA_SHAPES & 1, kChainNarrowL = (CHAIN_MFMA_SHAPES >> 1) & 1;
+
+// the product's launches: 128-frame tiles, then the smaller tiles, with the matrix-instruction shape of each phase as template arguments
+template <int NY, int NL>
+static void launch_chain_forms(TdnnChainParams p, hipStream_t s) {
+  const dim3 block(512);
+  if (p.n128 > 0) {
+    const dim3 grid(p.n128);
+    if (p.et == ET_F16) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_F16, 0, 4, NY, NL>), grid, block, 0, s, p);
+    else if (p.dbg != nullptr && p.dbg_fine) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 3, 4, NY, NL>), grid, block, 0, s, p);   // stamps only: results valid
+    else hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 0, 4, NY, NL>), grid, block, 0, s, p);
+  }
+  if (p.n_tail > 0) {
+    // the smaller tiles (chain_tile_plan): behind the full rounds, if any, on the same stream
+    p.row_base = p.n128 * 128; p.tile_base = p.n128;
+    p.dbg = nullptr;                                   // (the stamp buffer is laid out for the 128-frame launch)
+    const dim3 grid(p.n_tail);
+    if (p.tail_rows == 96) {
+      if (p.et == ET_F16) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_F16, 0, 3, NY, NL>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 0, 3, NY, NL>), grid, block, 0, s, p);
+    } else {
+      if (p.et == ET_F16) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_F16, 0, 2, NY, NL>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 0, 2, NY, NL>), grid, block, 0, s, p);
+    }
+  }
+}
+
 int launch_tdnn_chain(const TdnnChainParams &p0, hipStream_t s) {
   TdnnChainParams p = p0;
   constexpr int CM = 128;
@@ -618,9 +937,10 @@ int launch_tdnn_chain(const TdnnChainParams &p0, hipStream_t s) {
   ASV_REQUIRE(p.n_tail == 0 || p.tail_rows == 96 || p.tail_rows == 64, "tdnn(chain): tail tiles of %d frames", p.tail_rows);
   ASV_REQUIRE(p.n128 * 128 + p.n_tail * p.tail_rows >= p.rows && p.n128 * 128 <= p.rows, "tdnn(chain): tile plan %d x 128 + %d x %d does not cover %d rows", p.n128, p.n_tail,
               p.tail_rows, p.rows);
-  const dim3 block(512);
   p.row_base = 0; p.tile_base = 0;
 #ifdef ASV_WITH_ABLATION
+  const dim3 block(512);
+  int mfma = -1;
   // Developer build only (libasv_amd_dev.so, `make dev`): the ablation instantiations (results are garbage), the first pooling
   // epilogue and the four-wave kernel.  The switches are read ONCE per process; with ASV_AMD_LIVE_TUNE=1 (tools/chain_ab.py:
   // in-process interleaved A/B) at every launch.  The product library has none of this code: no environment variable reaches it.
@@ -632,6 +952,9 @@ int launch_tdnn_chain(const TdnnChainParams &p0, hipStream_t s) {
   // kernel (profiles/r3k_*): kept as the reproducible A/B of that design.
   static const int waves0 = read_int("ASV_AMD_CHAIN_WAVES");
   const int waves = live ? read_int("ASV_AMD_CHAIN_WAVES") : waves0;
+  // ASV_AMD_CHAIN_MFMA: bit 0 = the Y-writing phases, bit 1 = the last layer on the 16x16x32 shape (unset: as the product ships)
+  static const int mfma0 = read_int("ASV_AMD_CHAIN_MFMA");
+  mfma = live ? read_int("ASV_AMD_CHAIN_MFMA") : mfma0;
   if (p.n_tail == 0) {
     const dim3 grid(p.n128);
     if (waves == 4 && abl <= 0 && poolv != 0 && !(p.dbg != nullptr && p.dbg_fine) && tdnn_chain4_supported(p)) return launch_tdnn_chain4(p, s);
@@ -645,25 +968,14 @@ int launch_tdnn_chain(const TdnnChainParams &p0, hipStream_t s) {
     }
   }
 #endif
-  if (p.n128 > 0) {
-    const dim3 grid(p.n128);
-    if (p.et == ET_F16) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_F16>), grid, block, 0, s, p);
-    else if (p.dbg != nullptr && p.dbg_fine) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 3>), grid, block, 0, s, p);   // stamps only: results valid
-    else hipLaunchKernelGGL(tdnn_chain_kernel<1>, grid, block, 0, s, p);
-  }
-  if (p.n_tail > 0) {
-    // the smaller tiles (chain_tile_plan): behind the full rounds, if any, on the same stream
-    p.row_base = p.n128 * 128; p.tile_base = p.n128;
-    p.dbg = nullptr;                                   // (the stamp buffer is laid out for the 128-frame launch)
-    const dim3 grid(p.n_tail);
-    if (p.tail_rows == 96) {
-      if (p.et == ET_F16) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_F16, 0, 3>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 0, 3>), grid, block, 0, s, p);
-    } else {
-      if (p.et == ET_F16) hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_F16, 0, 2>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((tdnn_chain_kernel<1, ET_BF16, 0, 2>), grid, block, 0, s, p);
-    }
-  }
+#ifdef ASV_WITH_ABLATION
+  if (mfma == 0) launch_chain_forms<0, 0>(p, s);
+  else if (mfma == 1) launch_chain_forms<1, 0>(p, s);
+  else if (mfma == 2) launch_chain_forms<0, 1>(p, s);
+  else if (mfma == 3) launch_chain_forms<1, 1>(p, s);
+  else
+#endif
+  launch_chain_forms<kChainNarrowY, kChainNarrowL>(p, s);
   ASV_HIP_CHECK(hipGetLastError());
   return ASV_OK;
 }

@@ -11,12 +11,14 @@
 // matrix peak the chip reached, the load bandwidth over the chip, and the s_memtime count per iteration (NOT core cycles: a pure matrix
 // loop at 97 % of the 2.5 PF peak counts 24.4 per instruction where the pipe needs 32 core cycles - the counter runs at ~0.76 of the core clock there).
 //
-//   hipcc --offload-arch=gfx950 -O3 -o tools_vmem_probe tools/vmem_probe.hip && ./tools_vmem_probe
+//   hipcc --offload-arch=gfx950 -O3 -o tools_vmem_probe tools/vmem_probe.hip && ./tools_vmem_probe            (`./tools_vmem_probe shape`: only the
+//   32x32x16 / 16x16x32 A/B of probe_shape below)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -174,6 +176,113 @@ __global__ __launch_bounds__(512, 2) void calib(unsigned long long *res, float *
   }
 }
 
+// Matrix-instruction shape A/B (`tools_vmem_probe shape`, profiles/chain_mfma_shape_probe.txt): tdnn_chain_kernel's mix - 4 fragment loads of
+// 1 KiB spread over a half-iteration and fetched two ahead, R ds_read_b128, 8 waves of 128 accumulator registers per CU - on either
+//   NARROW = 0  16 x v_mfma_f32_32x32x16_bf16 on 8 accumulators of 16 registers, or
+//   NARROW = 1  32 x v_mfma_f32_16x16x32_bf16 on 32 accumulators of 4 registers: the same 128 x 64 wave tile over the same K = 32, the same
+//               operand bytes fetched, the same matrix-pipe cycles (16 per instruction against 32).
+// Every operand comes from `src` (the LDS image is a copy of its first 64 KiB), so the host decides the data: random bf16 or zeros - the
+// clock a loaded chip holds depends on the operand bits.  Per wave: s_memtime ticks and s_memrealtime (100 MHz) around the loop.
+typedef float v4f __attribute__((ext_vector_type(4)));
+template <int NARROW, int R>
+__global__ __launch_bounds__(512, 2) void probe_shape(const unsigned char *src, size_t region, int iters, float *out, unsigned long long *stamps) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[65536];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < 65536 / 16; i += 512) reinterpret_cast<uint4 *>(lds)[i] = reinterpret_cast<const uint4 *>(src)[i];
+  __syncthreads();
+  const unsigned char *base = src + (size_t)lane * 16;
+  uint4 xr[2], w[3][8];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) xr[k] = *reinterpret_cast<const uint4 *>(lds + wave * 8192 + k * 1024 + lane * 16);
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[d][k] = *reinterpret_cast<const uint4 *>(base + (size_t)(wave * 24 + d * 8 + k) * 1024);
+  v16f acc[8];
+  v4f accn[32];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[i][r] = 0.0f; accn[i * 4 + (r >> 2)][r & 3] = 0.0f; }
+  size_t off = (size_t)wave * 8 * 1024;
+  const unsigned long long r0 = __builtin_amdgcn_s_memrealtime(), t0 = __builtin_amdgcn_s_memtime();
+#pragma unroll 1
+  for (int it = 0; it < iters; it += 3) {
+#pragma unroll
+    for (int half = 0; half < 3; ++half) {
+      uint4 (&cur)[8] = w[half];
+      uint4 (&nxt)[8] = w[(half + 2) % 3];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        if (q % 4 == 0) nxt[q / 4] = *reinterpret_cast<const uint4 *>(base + off + (size_t)(q / 4) * 1024);
+        if (q < R) xr[q & 1] = *reinterpret_cast<const uint4 *>(lds + ((wave * 8192 + q * 1024 + lane * 16 + (int)(off >> 6)) & 65535 & ~15));
+        const v8b b = __builtin_bit_cast(v8b, xr[(q + 1) & 1]);
+        if constexpr (NARROW) {
+          accn[2 * q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8b, cur[q & 7]), b, accn[2 * q], 0, 0, 0);
+          accn[2 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8b, cur[(q + 4) & 7]), b, accn[2 * q + 1], 0, 0, 0);
+        } else {
+          acc[q & 7] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8b, cur[q & 7]), b, acc[q & 7], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      off += 64 * 1024;
+      if (off + 64 * 1024 > region) off = (size_t)wave * 8 * 1024;
+    }
+  }
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+  float s = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += NARROW ? accn[i * 4 + (r >> 2)][r & 3] : acc[i][r];
+  out[(size_t)blockIdx.x * 512 + threadIdx.x] = s;
+  if (lane == 0) { stamps[((size_t)blockIdx.x * 8 + wave) * 2] = t1 - t0; stamps[((size_t)blockIdx.x * 8 + wave) * 2 + 1] = r1 - r0; }
+}
+
+template <int NARROW, int R>
+static void run_shape(const unsigned char *src, size_t region, int wgs, int iters, float *out, unsigned long long *stamps, const char *data) {
+  hipLaunchKernelGGL((probe_shape<NARROW, R>), dim3(wgs), dim3(512), 0, 0, src, region, 66, out, stamps);        // warm
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  CK(hipEventRecord(e0));
+  hipLaunchKernelGGL((probe_shape<NARROW, R>), dim3(wgs), dim3(512), 0, 0, src, region, iters, out, stamps);
+  CK(hipEventRecord(e1));
+  CK(hipDeviceSynchronize());
+  float ms = 0;
+  CK(hipEventElapsedTime(&ms, e0, e1));
+  std::vector<unsigned long long> h((size_t)wgs * 16);
+  CK(hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost));
+  double ticks = 0, real = 0;
+  for (size_t i = 0; i < h.size(); i += 2) { ticks += (double)h[i]; real += (double)h[i + 1]; }
+  const double ns_it = (double)ms * 1e6 / iters;
+  printf("%-6s %-8s 4 loads + %2d LDS reads per 128 x 64 x 32 wave step: %6.1f ns per iteration = %5.1f %% of the bf16 matrix peak (2.5 PF); s_memtime %6.1f per iteration, %4.0f MHz in the kernel\n",
+         data, NARROW ? "16x16x32" : "32x32x16", R, ns_it, 100.0 * (double)wgs * 4 * 32 * 32768.0 / (ns_it * 1e-9) / 2.5e15, ticks / ((double)h.size() / 2) / iters, 100.0 * ticks / real);
+}
+
+// random bf16 of either sign in 0.25 .. 2 (every significand bit in use, sums of products stay far from overflow), or zeros
+static void shape_ab(unsigned char *src, size_t bytes, size_t region, int cus, float *out) {
+  unsigned long long *stamps = nullptr;
+  CK(hipMalloc(&stamps, (size_t)cus * 16 * 8));
+  std::vector<uint16_t> host(bytes / 2);
+  for (int data = 0; data < 2; ++data) {
+    uint64_t st = 0x9e3779b97f4a7c15ull;
+    for (auto &v : host) {
+      st = st * 6364136223846793005ull + 1442695040888963407ull;
+      const uint32_t r = (uint32_t)(st >> 33);
+      v = data == 0 ? (uint16_t)(((r & 1u) << 15) | ((125u + ((r >> 1) % 3u)) << 7) | ((r >> 8) & 0x7fu)) : (uint16_t)0;
+    }
+    CK(hipMemcpy(src, host.data(), bytes, hipMemcpyHostToDevice));
+    const int iters = 4098;
+    for (int round = 0; round < 4; ++round) {
+      run_shape<0, 8>(src, region, cus, iters, out, stamps, data == 0 ? "random" : "zeros");
+      run_shape<1, 8>(src, region, cus, iters, out, stamps, data == 0 ? "random" : "zeros");
+      run_shape<0, 16>(src, region, cus, iters, out, stamps, data == 0 ? "random" : "zeros");
+      run_shape<1, 16>(src, region, cus, iters, out, stamps, data == 0 ? "random" : "zeros");
+    }
+  }
+  CK(hipFree(stamps));
+}
+
 static int cus_g = 256;
 template <int L, int D = 1, int S = 1, int R = 0>
 static void run(const unsigned char *src, size_t region, size_t wg_stride, int wgs, int iters, float *out, unsigned long long *cyc, const char *what) {
@@ -198,7 +307,7 @@ static void run(const unsigned char *src, size_t region, size_t wg_stride, int w
          what, L, R, S, D, ns_it, 100.0 * (double)cus_g * 4 * 32 * 32768.0 / (ns_it * 1e-9) / 2.5e15, (double)cus_g * 8.0 * L * 1024.0 / (ns_it * 1e-9) / 1e12, per_it);
 }
 
-int main() {
+int main(int argc, char **argv) {
   int dev = 0, cus = 256;
   CK(hipGetDevice(&dev));
   CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -212,6 +321,10 @@ int main() {
   CK(hipMemset(src, 0x3f, bytes));
   CK(hipMalloc(&out, (size_t)cus * 512 * 4));
   CK(hipMalloc(&cyc, (size_t)cus * 8 * 8));
+  if (argc > 1 && std::string(argv[1]) == "shape") {   // the matrix-instruction shape A/B alone
+    shape_ab(src, bytes, shared_region, cus, out);
+    return 0;
+  }
   for (int load = 0; load < 2; ++load) {
     unsigned long long *res = nullptr;
     CK(hipMalloc(&res, (size_t)cus * 16));
