@@ -256,6 +256,7 @@ SYMBOLS = [
     "asv_ingest_frames", "asv_decode_compressed", "asv_ingest_windows", "asv_desilence_pcm16",
     "asv_net_define_grid_reach", "asv_net_add_grid_conv",
     "asv_net_define_grid_valid", "asv_net_add_front_conv", "asv_net_add_posenc", "asv_net_add_self_attention",
+    "asv_encode_compressed",
 ]
 
 
@@ -351,6 +352,7 @@ def lib():
     L.asv_ingest_frames.argtypes = [vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp, vp]
     L.asv_ingest_windows.argtypes = [vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci, ci, ci, ci, ci, ci, vp, vp]
     L.asv_decode_compressed.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte), ci, ci, vp, vp]
+    L.asv_encode_compressed.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte), ci, ci, vp, vp, vp]
     L.asv_desilence_pcm16.argtypes = [vp, C.POINTER(C.c_longlong), ci, ci, C.c_double, vp, C.POINTER(C.c_longlong), vp]
     L.asv_cmvn.argtypes = [vp, C.POINTER(C.c_longlong), ci, ci, ci, ci, C.c_float, vp]
     for name in SYMBOLS:

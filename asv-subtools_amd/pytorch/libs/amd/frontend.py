@@ -481,3 +481,58 @@ def decode_compressed(bytes_dev, byte_off, frame_off, formats, dim, out=None):
                                                     formats.ctypes.data_as(C.POINTER(C.c_ubyte)), n, dim, C.c_void_p(out.data_ptr()),
                                                     C.c_void_p(torch.cuda.current_stream(bytes_dev.device).cuda_stream)), "asv_decode_compressed")
     return out[:rows]
+
+
+def compressed_auto_format(rows):
+    """Kaldi's automatic compression method (what copy-feats --compress=true uses): more than 8 rows -> 'CM ' (1), otherwise 'CM2' (2)."""
+    return np.where(np.asarray(rows) > 8, 1, 2).astype(np.uint8)
+
+
+def encode_compressed(feats, frame_off, out=None, formats=None):
+    """Packed float32 rows on the device -> the bodies of Kaldi compressed matrices, as they lie on disk behind the token, in three
+    launches on the current stream (asv_encode_compressed, DESIGN 4.3.5).  feats: contiguous [frame_off[-1], dim] f32 CUDA tensor;
+    frame_off: int64 [n + 1] from 0, every utterance at least one row.  The format of each utterance is Kaldi's automatic choice
+    (compressed_auto_format; `formats` overrides it, 1 / 2 per utterance) and the bodies are laid out one behind the other, each at a
+    16-byte boundary of `out` (a contiguous 1-D uint8 CUDA tensor that starts at one; allocated when not given - only the bodies are
+    written, the padding bytes between them keep what they held).  Returns (bytes uint8 CUDA tensor, byte_off int64 [n], formats
+    uint8 [n], status int32 CUDA tensor [n]: 0 = ok, 1 = the utterance holds a NaN or an infinity and its body is unspecified).  Body u
+    is bytes[byte_off[u] : byte_off[u] + compressed_body_bytes(formats[u], rows[u], dim)]; no synchronisation in here."""
+    import torch
+    frame_off = _off(frame_off)
+    n = len(frame_off) - 1
+    if feats.dim() != 2 or feats.dtype != torch.float32 or not feats.is_cuda or not feats.is_contiguous() or n < 1 or int(frame_off[-1]) != feats.shape[0]:
+        raise ValueError("encode_compressed: feats must be a contiguous [frame_off[-1], dim] f32 CUDA tensor")
+    rows_of = np.diff(frame_off)
+    if int(frame_off[0]) != 0 or (rows_of < 1).any():
+        raise ValueError("encode_compressed: frame_off must start at 0 and increase (an empty matrix has no compressed form)")
+    dim = int(feats.shape[1])
+    if dim < 1:
+        raise ValueError("encode_compressed: dim %d" % dim)
+    formats = compressed_auto_format(rows_of) if formats is None else np.ascontiguousarray(formats, dtype=np.uint8)
+    if len(formats) != n or not np.isin(formats, (1, 2)).all():
+        raise ValueError("encode_compressed: one format per utterance, 1 ('CM ') or 2 ('CM2')")
+    sizes = (compressed_body_bytes(formats, rows_of, dim) + 15) // 16 * 16
+    byte_off = np.zeros(n, dtype=np.int64)
+    np.cumsum(sizes[:-1], out=byte_off[1:])
+    total = int(byte_off[-1] + sizes[-1])
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=feats.device)
+    elif out.dim() != 1 or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.shape[0] < total or out.data_ptr() % 16:
+        raise ValueError("encode_compressed: out must be a contiguous 1-D uint8 CUDA tensor of at least %d bytes at a 16-byte boundary" % total)
+    status = torch.empty(n, dtype=torch.int32, device=feats.device)
+    with torch.cuda.device(feats.device):
+        capi.check(capi.lib().asv_encode_compressed(C.c_void_p(feats.data_ptr()), _i64p(frame_off), _i64p(byte_off), formats.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                    n, dim, C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()),
+                                                    C.c_void_p(torch.cuda.current_stream(feats.device).cuda_stream)), "asv_encode_compressed")
+    return out[:total], byte_off, formats, status
+
+
+def read_wav_pcm16(path):
+    """(int16 samples of channel 0, sample rate).  16-bit PCM only - anything else is an error, not a silent conversion."""
+    import wave
+    with wave.open(path, "rb") as f:
+        if f.getsampwidth() != 2 or f.getcomptype() != "NONE":
+            raise ValueError("%s: only 16-bit PCM WAV is supported (sample width %d, %s)" % (path, f.getsampwidth(), f.getcomptype()))
+        ch, sr, n = f.getnchannels(), f.getframerate(), f.getnframes()
+        data = np.frombuffer(f.readframes(n), dtype="<i2")
+    return (data.reshape(-1, ch)[:, 0] if ch > 1 else data), sr

@@ -766,3 +766,48 @@ def write_vec_flt_ark_scp(ark_path, scp_path, items):
             ark.write((key + " ").encode("latin1"))
             scp.write("%s %s:%d\n" % (key, os.path.abspath(ark_path), ark.tell()))
             write_vec_flt(ark, np.ascontiguousarray(vec), key="")
+
+
+COMPRESSED_TOKENS = {1: b"CM ", 2: b"CM2 ", 3: b"CM3 "}
+
+
+class ArkScpWriter(object):
+    """One binary ark and its scp, written entry by entry: write(key, payload) puts `key SP payload` into the ark (payload: the entry
+    from its \\0B on, any bytes-like objects) and 'key abs_path:offset' - the offset of the \\0B - into the scp."""
+
+    def __init__(self, ark_path, scp_path):
+        self.path = os.path.abspath(ark_path)
+        self.ark, self.scp = open(ark_path, "wb"), open(scp_path, "w")
+
+    def write(self, key, *payload):
+        self.ark.write((key + " ").encode("latin1"))
+        self.scp.write("%s %s:%d\n" % (key, self.path, self.ark.tell()))
+        for part in payload:
+            self.ark.write(part)
+
+    def close(self):
+        self.ark.close()
+        self.scp.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def float_matrix_head(rows, cols):
+    """`\\0BFM ` and the two counts: what write_mat puts in front of the float32 data."""
+    return b"\0BFM \4" + struct.pack("<I", rows) + b"\4" + struct.pack("<I", cols)
+
+
+def write_compressed_ark_scp(ark_path, scp_path, items):
+    """Writes (key, format, body) triples - format 1 = 'CM ', 2 = 'CM2', 3 = 'CM3'; body: the bytes of a Kaldi compressed matrix from its
+    16-byte global header on, as libs.amd.frontend.encode_compressed produces them - as `key SP \\0B token body` entries to `ark_path`
+    and the matching 'key path:offset' lines (offset: at the \\0B, like write_vec_flt_ark_scp) to `scp_path`: what
+    `copy-feats --compress=true ark:- ark,scp:...` does in steps/make_fbank.sh."""
+    with ArkScpWriter(ark_path, scp_path) as w:
+        for key, fmt, body in items:
+            if int(fmt) not in COMPRESSED_TOKENS:
+                raise UnknownMatrixHeader("compressed format %r of '%s' (1 = 'CM ', 2 = 'CM2', 3 = 'CM3')" % (fmt, key))
+            w.write(key, b"\0B" + COMPRESSED_TOKENS[int(fmt)], body)

@@ -39,7 +39,6 @@ import os
 import sys
 import time
 import traceback
-import wave
 
 sys.path.insert(0, "subtools/pytorch")
 sys.path.insert(0, os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")))
@@ -74,14 +73,7 @@ def get_args(argv=None):
     return parser.parse_args(argv)
 
 
-def read_wav_pcm16(path):
-    """(int16 samples of channel 0, sample rate).  16-bit PCM only - anything else is an error, not a silent conversion."""
-    with wave.open(path, "rb") as f:
-        if f.getsampwidth() != 2 or f.getcomptype() != "NONE":
-            raise ValueError("%s: only 16-bit PCM WAV is supported (sample width %d, %s)" % (path, f.getsampwidth(), f.getcomptype()))
-        ch, sr, n = f.getnchannels(), f.getframerate(), f.getnframes()
-        data = np.frombuffer(f.readframes(n), dtype="<i2")
-    return (data.reshape(-1, ch)[:, 0] if ch > 1 else data), sr
+read_wav_pcm16 = frontend.read_wav_pcm16          # (shared with makeFeatures.py)
 
 
 def check_args(args):

@@ -744,6 +744,25 @@ int asv_ingest_windows(const float *feats, long long n_rows, const long long *wi
  * stream synchronisation, the caller's arrays may be reused on return. */
 int asv_decode_compressed(const unsigned char *bytes, const long long *byte_offsets, const long long *frame_offsets,
                           const unsigned char *formats, int n_utts, int dim, float *out, void *stream);
+/* The way back: packed float32 rows -> the BODIES of Kaldi compressed matrices, as copy-feats --compress=true lays them on
+ * disk behind the token (Kaldi's automatic method: the callers give 'CM ' to matrices of more than 8 rows, 'CM2' to the
+ * others; 'CM3' is never written and refused here).  feats: device [frame_offsets[n_utts]][dim] row-major, utterances back
+ * to back; frame_offsets: host int64 [n_utts+1] from 0, increasing (an empty utterance has no compressed form); formats:
+ * host bytes [n_utts], 1 = 'CM ', 2 = 'CM2'; byte_offsets: host int64 [n_utts], start of each body in `bytes`, a multiple
+ * of 16, increasing, bodies not overlapping (their sizes: 16 + 8 dim + rows dim for 'CM ', 16 + 2 rows dim for 'CM2').
+ * bytes: device; utterance u's body is written from its 16-byte global header {float min, float range, int32 rows, int32
+ * cols} on, and no byte outside the bodies is written - the up to 15 padding bytes between two bodies included.  status:
+ * device int32 [n_utts]: 0 = ok, 1 = the utterance holds a NaN or an infinity (Kaldi asserts on such input); its body is
+ * then unspecified, but stays inside its span.  The quantiser is compressed-matrix.cc restated: sequential
+ * float32, no FMA, correctly rounded divisions, truncating conversions, exact order statistics for any row count; what is
+ * pinned is that asv_decode_compressed and the host reader decode the bytes, and that they equal a NumPy restatement of
+ * the rule byte for byte - not Kaldi's own writer.  Negative return, and no launch: a null pointer, n_utts < 1, dim < 1,
+ * frame offsets that do not increase, a byte offset that is no multiple of 16, overlapping bodies, a format other than 1
+ * or 2.  The offsets are staged by the library as asv_ingest_frames stages its own: no stream synchronisation, the
+ * caller's arrays may be reused on return. */
+int asv_encode_compressed(const float *feats, const long long *frame_offsets, const long long *byte_offsets,
+                          const unsigned char *formats, int n_utts, int dim, unsigned char *bytes, int *status,
+                          void *stream);
 /* processor.py:149-175 / signal_processing.py:13-55 on 16-bit PCM in HBM, in front of asv_fbank_pcm16: the reference's
  * --de-silence waveform trimming.  An utterance of L samples is cut into L / win_samples full blocks and, if any samples
  * remain, one tail block of them; a block of m samples is kept iff sum |s_i| > min_eng * m (the sum an exact integer,
