@@ -38,6 +38,16 @@
 //   * Production = tdnn_gemm_p8p_kernel further down: this schedule inside a persistent tile loop (the next tile's first K-tile is
 //     requested in front of the epilogue).  The one-tile kernel here stays for A/B (variant 50) and carries the measurement variants.
 //   * Epilogue: kernels_tdnn_v3.hip's (bias -> ReLU -> folded BN, packed 16-bit, wave-private LDS transpose, 16-byte row stores).
+//   * The persistent production kernel runs its K loop on v_mfma_f32_16x16x32 (template argument NARROW, see there): same wave tile,
+//     same LDS image, same reads, bit-identical output.  On random bf16 (tools/p8_probe, x-vector tdnn2, 408 tiles x 24 K-tiles) the
+//     kernel takes 71.6 us (70.3 - 73.8 over 7 interleaved rounds) against 76.3 us (75.1 - 77.2) on 32x32x16, while wave 0 counts
+//     2445 s_memtime ticks per K-tile against 2413: the narrow shape is not shorter in ticks, the chip holds a higher clock under it
+//     (profiles/p8_mfma_shape_probe.txt); in the model 314.9 -> 311.4 us per x-vector step and 2816 -> 2758 us per ECAPA step, ranges
+//     apart, no LDS bank conflicts on either shape (profiles/p8_mfma_shape_ab.txt, _lds_conflicts.txt).  Registers (-Rpass-analysis=kernel-resource-usage): 256 VGPRs, no spill, no scratch on the
+//     narrow shape in all four instantiations, 252 / 253 on the wide one.  The one-tile kernel and its variants stay on 32x32x16.
+//     Tried and dropped: keeping both HA0 / HA1 source offsets of the one-tap form per lane (as the one-tile kernel does) - with the
+//     narrow shape's allocation that form spilled 4 registers (20 bytes of scratch, which the counted waits cannot afford); HA1's offset
+//     is HA0's + 64 rows, inside the tile, so it now travels in the scalar base.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -481,13 +491,33 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8_kernel(const TdnnKernelPa
 constexpr int P8P_PAR_SLOT = 4096;                  // bias | scale | shift (3 x 1 KiB) | row-validity words (1 KiB piece, 32 B used)
 constexpr int P8P_LDS_BYTES = 2 * P8_BUF + 2 * P8P_PAR_SLOT;
 
-template <int ET, bool ONE_TAP>
+//
+// NARROW: the K loop on v_mfma_f32_16x16x32 (mfma16n) instead of v_mfma_f32_32x32x16.  The wave tile is the same 128 frames x 64
+// channels, as 8 x 4 accumulators of 4 registers: D = W . X^T with A = 16 channels x 32 k, B = 32 k x 16 frames, so a lane
+// (lc = lane & 15, lo = lane >> 4) holds frame 16 f + lc and channels 16 cf + 4 lo + e.  A 64-channel K-tile is two k-steps of 32;
+// a phase consumes exactly the half-tiles it consumes on the wide shape (HA0 = frame fragments 0 - 3, HA1 = 4 - 7, HB0 = channel
+// fragments 0 - 1, HB1 = 2 - 3) with the same number of ds_read_b128 (8 per A half-tile, 4 per B half-tile) into the same 64 operand
+// registers, so the staging, the counted waits, the stagger, the barriers and the RAW / WAR argument above hold word for word; a
+// cluster is 32 instructions of 16 matrix-pipe cycles instead of 16 of 32.  Every accumulator takes its k in ascending order and
+// the epilogue evaluates the same expression on the same 4-channel groups: the output is bit-identical to the wide shape's.
+//   LDS reads: lane (lc, lo) reads row lc (+ 16 per fragment: an immediate offset, (row >> 1) & 7 does not change), 16-byte slot
+//   (4 ks + lo) ^ ((lc >> 1) & 7).  ds_read_b128 serves four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
+//   same + 32); in each the 8 row pairs present carry 8 different slots and the two rows of a pair lie 128 bytes apart, so the 16
+//   lanes cover all 64 banks once: conflict-free with the unchanged swizzle (first group, ks = 0: slots 0 1 6 7 | 3 2 5 4).
+//   Epilogue scratch: a lane writes 8 bytes = its 4 channels of frame 16 f + lc at slot 2 cf + (lo >> 1), half lo & 1.
+// STAMP (developer build): s_memtime of wave 0 around the first tile's K loop into p.partial[workgroup][8] (1 start, 2 end).
+template <int ET, bool ONE_TAP, bool NARROW, bool STAMP = false>
 __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelParams p, int m_tiles, int n_tiles) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[P8P_LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int lr = lane & 31, lh = lane >> 5;
+  const int lr = NARROW ? (lane & 15) : (lane & 31), lh = NARROW ? (lane >> 4) : (lane >> 5);      // NARROW: (lc, lo)
+  auto stamp = [&](int k) {
+    if constexpr (STAMP) {
+      if (tid == 0) reinterpret_cast<unsigned long long *>(p.partial)[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime();
+    }
+  };
   const int total = m_tiles * n_tiles;
   const int grid = gridDim.x;
 
@@ -503,7 +533,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
   const int g_row = lane >> 3, g_slot = lane & 7;
 
   // per-tile, per-lane DMA source offsets (see the one-tile kernel)
-  struct TileAddr { int m0, n0; int a_row[2]; uint32_t a_slot[2], a_voff[2][2], b_off[2]; };
+  struct TileAddr { int m0, n0; int a_row[2]; uint32_t a_slot[2], a_voff[2], b_off[2]; };
   auto tile_addr = [&](int it) {
     TileAddr t;
     const int tile = xcd_swizzle(it, total);
@@ -515,8 +545,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
       const uint32_t slot16 = (uint32_t)(g_slot ^ ((r >> 1) & 7)) * 16u;
       t.a_row[i] = t.m0 + (r >> 6) * 128 + (r & 63);
       t.a_slot[i] = slot16;
-      t.a_voff[0][i] = (uint32_t)t.a_row[i] * x_pitch + slot16;
-      t.a_voff[1][i] = (uint32_t)min(t.a_row[i] + 64, last_row) * x_pitch + slot16;
+      t.a_voff[i] = (uint32_t)t.a_row[i] * x_pitch + slot16;      // ONE_TAP: HA0; HA1 is 64 rows on (inside the tile: no clamp), added to the scalar base
       t.b_off[i] = (uint32_t)(t.n0 + (r >> 5) * 64 + (r & 31)) * w_pitch + slot16;
     }
     return t;
@@ -531,8 +560,9 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
     if (which & 1) {
       const unsigned char *base = xg + (size_t)c * 128;
       if (ONE_TAP) {
+        const unsigned char *base1 = base + (which == 3 ? (size_t)64 * x_pitch : 0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) glds16_s_m0(base, T.a_voff[which == 3][i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
+        for (int i = 0; i < 2; ++i) glds16_s_m0(base1, T.a_voff[i], __builtin_amdgcn_readfirstlane(dst0 + i * 1024u));
       } else {
         const int d = __builtin_amdgcn_readlane(v_taps, t) + (which == 3 ? 64 : 0);
 #pragma unroll
@@ -567,16 +597,42 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
 
   const uint32_t sw = (uint32_t)((lr >> 1) & 7);
   const uint32_t a_base = (uint32_t)(wm * 64 + lr) * P8_ROWB, b_base = (uint32_t)(wn * 32 + lr) * P8_ROWB;
-  uint32_t a_addr[4], b_addr[4];
+  uint32_t a_addr[4], b_addr[4];          // wide: per k-group of 16; NARROW: per k-step of 32 (entries 0 and 1)
 #pragma unroll
   for (int kg = 0; kg < 4; ++kg) {
-    const uint32_t s16 = (((uint32_t)(kg * 2 + lh)) ^ sw) * 16u;
+    const uint32_t s16 = (((uint32_t)(NARROW ? kg * 4 + lh : kg * 2 + lh)) ^ sw) * 16u;
     a_addr[kg] = a_base + s16;
     b_addr[kg] = b_base + s16;
   }
   auto barrier = [&]() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+  };
+  // fragment reads of a half-tile.  Wide: 4 k-groups (x 2 frame fragments of 32 rows).  NARROW: 2 k-steps x 2 channel fragments
+  // (wfr[ks * 2 + c2]) / 4 frame fragments (xa[f4 * 2 + ks]) of 16 rows.
+  auto read_b = [&](const unsigned char *H, uint4 (&wfr)[4]) {
+    if constexpr (NARROW) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2) wfr[ks * 2 + c2] = *reinterpret_cast<const uint4 *>(H + c2 * (16 * P8_ROWB) + b_addr[ks]);
+    } else {
+#pragma unroll
+      for (int kg = 0; kg < 4; ++kg) wfr[kg] = *reinterpret_cast<const uint4 *>(H + b_addr[kg]);
+    }
+  };
+  auto read_a = [&](const unsigned char *H, uint4 (&xa)[8]) {
+    if constexpr (NARROW) {
+#pragma unroll
+      for (int f4 = 0; f4 < 4; ++f4)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) xa[f4 * 2 + ks] = *reinterpret_cast<const uint4 *>(H + f4 * (16 * P8_ROWB) + a_addr[ks]);
+    } else {
+#pragma unroll
+      for (int kg = 0; kg < 4; ++kg)
+#pragma unroll
+        for (int i2 = 0; i2 < 2; ++i2) xa[i2 * 4 + kg] = *reinterpret_cast<const uint4 *>(H + i2 * (32 * P8_ROWB) + a_addr[kg]);
+    }
   };
   auto kt_ct = [&](int kt, int &c, int &t) { c = kt / n_taps; t = kt - c * n_taps; };
   const float act_lo = (p.act1 == ASV_ACT_RELU) ? 0.0f : -INFINITY;
@@ -599,20 +655,42 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
     if (nkt > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     barrier();
-    f32x16_t acc[4][2];
+    f32x16_t acc[4][2];                     // wide: [frame fragment of 32][channel fragment of 32]
+    f32x4_t accn[8][4];                     // NARROW: [frame fragment of 16][channel fragment of 16]
+    if constexpr (NARROW) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+      for (int f = 0; f < 8; ++f)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+        for (int cf = 0; cf < 4; ++cf)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    uint4 wb0[4], wb1[4], xa[2][4];
+          for (int r = 0; r < 4; ++r) accn[f][cf][r] = 0.0f;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    }
+    uint4 wb0[4], wb1[4], xa[8];
+    if (it == (int)blockIdx.x) stamp(1);
     if (wm == 1) __builtin_amdgcn_s_barrier();                 // this wave row runs one barrier behind the other inside the K loop
+    // one quadrant: channel half j (HB0 / HB1) x frame half i0 / 2 (HA0 / HA1); k ascending per accumulator on both shapes
     auto mma_q = [&](const uint4 (&wfr)[4], int j, int i0) {
+      if constexpr (NARROW) {
 #pragma unroll
-      for (int kg = 0; kg < 4; ++kg)
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) acc[i0 + i2][j] = mfma16<ET>(wfr[kg], xa[i2][kg], acc[i0 + i2][j]);
+          for (int f4 = 0; f4 < 4; ++f4)
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2)
+              accn[i0 * 2 + f4][j * 2 + c2] = mfma16n<ET>(wfr[ks * 2 + c2], xa[f4 * 2 + ks], accn[i0 * 2 + f4][j * 2 + c2]);
+      } else {
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg)
+#pragma unroll
+          for (int i2 = 0; i2 < 2; ++i2) acc[i0 + i2][j] = mfma16<ET>(wfr[kg], xa[i2 * 4 + kg], acc[i0 + i2][j]);
+      }
     };
     int c1 = 0, t1 = 0, c2 = 0, t2 = 0;
     auto adv = [&](int &c, int &t) { if (++t == n_taps) { t = 0; ++c; } };
@@ -621,14 +699,9 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
       constexpr int TAIL = decltype(tail_c)::value;
       const int b = kt & 1;
       const unsigned char *L = lds + (uint32_t)b * P8_BUF;
-#pragma unroll
-      for (int kg = 0; kg < 4; ++kg) wb0[kg] = *reinterpret_cast<const uint4 *>(L + P8_OFF_B0 + b_addr[kg]);
-#pragma unroll
-      for (int kg = 0; kg < 4; ++kg)
-#pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) xa[i2][kg] = *reinterpret_cast<const uint4 *>(L + P8_OFF_A0 + i2 * (32 * P8_ROWB) + a_addr[kg]);
-#pragma unroll
-      for (int kg = 0; kg < 4; ++kg) wb1[kg] = *reinterpret_cast<const uint4 *>(L + P8_OFF_B1 + b_addr[kg]);
+      read_b(L + P8_OFF_B0, wb0);
+      read_a(L + P8_OFF_A0, xa);
+      read_b(L + P8_OFF_B1, wb1);
       __builtin_amdgcn_sched_barrier(0);
       if (TAIL <= 1) { stage(cur, 2, c1, t1, b ^ 1); stage(cur, 3, c1, t1, b ^ 1); }
       if (TAIL <= 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
@@ -641,10 +714,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       barrier();
-#pragma unroll
-      for (int kg = 0; kg < 4; ++kg)
-#pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) xa[i2][kg] = *reinterpret_cast<const uint4 *>(L + P8_OFF_A1 + i2 * (32 * P8_ROWB) + a_addr[kg]);
+      read_a(L + P8_OFF_A1, xa);
       __builtin_amdgcn_sched_barrier(0);
       if (TAIL == 0) { stage(cur, 0, c2, t2, b); stage(cur, 1, c2, t2, b); }
       if (TAIL == 0) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
@@ -667,6 +737,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
     ktile2(kt, J2{});
     if (wm == 0) __builtin_amdgcn_s_barrier();                 // the rows meet again: nobody reads the buffers any more, no DMA in flight
     asm volatile("" ::: "memory");
+    if (it == (int)blockIdx.x) stamp(2);
 
     // ---- the next tile's parameters and first K-tile, requested in front of this tile's epilogue
     const bool has_next = it + grid < total;
@@ -683,32 +754,62 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
       unsigned char *scr = lds + P8_BUF + wave * (64 * P8_ROWB);        // [64 frames][64 channels] 16-bit, 128-B rows, swizzled slots
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        uint32_t vmask = 0;
+        if constexpr (NARROW) {
+          // accn[f][cf][e]: frame = m0 + wm*128 + f*16 + lc, channel = n0 + wn*64 + cf*16 + 4*lo + e
+          uint32_t vmask = 0;
 #pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2) vmask |= ((vw[wm * 4 + h * 2 + i2] >> lr) & 1u) << i2;
+          for (int f4 = 0; f4 < 4; ++f4) vmask |= ((vw[wm * 4 + h * 2 + (f4 >> 1)] >> ((f4 & 1) * 16 + lr)) & 1u) << f4;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int chl = wn * 64 + j * 32 + 8 * q + 4 * lh;
+          for (int cf = 0; cf < 4; ++cf) {
+            const int chl = wn * 64 + cf * 16 + 4 * lh;
             const float4 b4 = *reinterpret_cast<const float4 *>(par + chl);
             const float4 sc4 = *reinterpret_cast<const float4 *>(par + 256 + chl);
             const float4 sh4 = *reinterpret_cast<const float4 *>(par + 512 + chl);
             const float b[4] = {b4.x, b4.y, b4.z, b4.w}, sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
-            const int sl = j * 4 + q;
+            const int sl = cf * 2 + (lh >> 1);       // channel offset cf*16 + 4*lo -> 16-B slot, 8-B half lo & 1
 #pragma unroll
-            for (int i2 = 0; i2 < 2; ++i2) {
-              const bool valid = (vmask >> i2) & 1u;
-              const int frow = i2 * 32 + lr;
+            for (int f4 = 0; f4 < 4; ++f4) {
+              const bool valid = (vmask >> f4) & 1u;
+              const int frow = f4 * 16 + lr;
               float y[4];
 #pragma unroll
-              for (int e = 0; e < 4; ++e) y[e] = tdnn_epilogue_fast(acc[h * 2 + i2][j][q * 4 + e], b[e], act_lo, sc[e], sh[e], true);
+              for (int e = 0; e < 4; ++e) y[e] = tdnn_epilogue_fast(accn[h * 4 + f4][cf][e], b[e], act_lo, sc[e], sh[e], true);
               uint2 pk;
               pk.x = pack_h16x2<ET>(y[0], y[1]);
               pk.y = pack_h16x2<ET>(y[2], y[3]);
               pk.x = valid ? pk.x : 0u;
               pk.y = valid ? pk.y : 0u;
-              *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + lds_swz(frow, sl) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
+              *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + lds_swz(frow, sl) * 16 + (((lh & 1) ^ (frow & 1)) * 8)) = pk;
+            }
+          }
+        } else {
+          uint32_t vmask = 0;
+#pragma unroll
+          for (int i2 = 0; i2 < 2; ++i2) vmask |= ((vw[wm * 4 + h * 2 + i2] >> lr) & 1u) << i2;
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int chl = wn * 64 + j * 32 + 8 * q + 4 * lh;
+              const float4 b4 = *reinterpret_cast<const float4 *>(par + chl);
+              const float4 sc4 = *reinterpret_cast<const float4 *>(par + 256 + chl);
+              const float4 sh4 = *reinterpret_cast<const float4 *>(par + 512 + chl);
+              const float b[4] = {b4.x, b4.y, b4.z, b4.w}, sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
+              const int sl = j * 4 + q;
+#pragma unroll
+              for (int i2 = 0; i2 < 2; ++i2) {
+                const bool valid = (vmask >> i2) & 1u;
+                const int frow = i2 * 32 + lr;
+                float y[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] = tdnn_epilogue_fast(acc[h * 2 + i2][j][q * 4 + e], b[e], act_lo, sc[e], sh[e], true);
+                uint2 pk;
+                pk.x = pack_h16x2<ET>(y[0], y[1]);
+                pk.y = pack_h16x2<ET>(y[2], y[3]);
+                pk.x = valid ? pk.x : 0u;
+                pk.y = valid ? pk.y : 0u;
+                *reinterpret_cast<uint2 *>(scr + frow * P8_ROWB + lds_swz(frow, sl) * 16 + ((lh ^ (frow & 1)) * 8)) = pk;
+              }
             }
           }
         }
@@ -734,6 +835,23 @@ __global__ __launch_bounds__(512, 2) void tdnn_gemm_p8p_kernel(const TdnnKernelP
     slot ^= 1;
     it += grid;
   }
+}
+
+// Which matrix-instruction shape the persistent kernel ships with (1 = 16x16x32): decided by wall clock, profiles/p8_mfma_shape_ab.txt.
+// The other instantiation exists in the developer build only (ASV_AMD_P8_MFMA in launch_tdnn_p8_variant).
+#ifndef P8_MFMA_NARROW
+#define P8_MFMA_NARROW 1
+#endif
+constexpr bool kP8Narrow = P8_MFMA_NARROW != 0;
+
+template <bool NARROW>
+void launch_p8p(const TdnnKernelParams &p, bool one, dim3 grid, int m_tiles, int n_tiles, hipStream_t s) {
+  const dim3 block(512);
+  const bool f16 = p.et == ET_F16;
+  if (one) { if (f16) hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_F16, true, NARROW>), grid, block, 0, s, p, m_tiles, n_tiles);
+             else hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, true, NARROW>), grid, block, 0, s, p, m_tiles, n_tiles); }
+  else { if (f16) hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_F16, false, NARROW>), grid, block, 0, s, p, m_tiles, n_tiles);
+         else hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, false, NARROW>), grid, block, 0, s, p, m_tiles, n_tiles); }
 }
 
 }  // namespace
@@ -783,10 +901,28 @@ int launch_tdnn_p8_variant(const TdnnKernelParams &p, int variant, hipStream_t s
         cus = n > 0 ? n : 256;
       }
       const dim3 pgrid(std::min(m_tiles * n_tiles, cus));
-      if (one) { if (f16) hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_F16, true>), pgrid, block, 0, s, p, m_tiles, n_tiles);
-                 else hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, true>), pgrid, block, 0, s, p, m_tiles, n_tiles); }
-      else { if (f16) hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_F16, false>), pgrid, block, 0, s, p, m_tiles, n_tiles);
-             else hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, false>), pgrid, block, 0, s, p, m_tiles, n_tiles); }
+#ifdef ASV_WITH_ABLATION
+      // Developer build only: ASV_AMD_P8_MFMA = 0 / 1 picks the matrix-instruction shape (unset: as the product ships), read once per
+      // process, with ASV_AMD_LIVE_TUNE=1 at every launch (tools/chain_ab.py).  Variants 60 / 61 name the shape outright, 62 / 63 are
+      // their bf16 forms with the K-loop stamps of the first tile (tools/p8_probe; p.partial = 64 bytes per workgroup).
+      static const bool live = getenv("ASV_AMD_LIVE_TUNE") != nullptr;
+      auto read_int = [](const char *name) { const char *v = getenv(name); return v != nullptr ? atoi(v) : -1; };
+      static const int mfma0 = read_int("ASV_AMD_P8_MFMA");
+      int shape = live ? read_int("ASV_AMD_P8_MFMA") : mfma0;
+      if (variant == 60 || variant == 62) shape = 0;
+      if (variant == 61 || variant == 63) shape = 1;
+      if (variant == 62 || variant == 63) {
+        ASV_REQUIRE(!f16 && p.partial != nullptr, "tdnn(p8): the stamped forms are bf16 and write p.partial");
+        if (variant == 62) { if (one) hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, true, false, true>), pgrid, block, 0, s, p, m_tiles, n_tiles);
+                             else hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, false, false, true>), pgrid, block, 0, s, p, m_tiles, n_tiles); }
+        else { if (one) hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, true, true, true>), pgrid, block, 0, s, p, m_tiles, n_tiles);
+               else hipLaunchKernelGGL((tdnn_gemm_p8p_kernel<ET_BF16, false, true, true>), pgrid, block, 0, s, p, m_tiles, n_tiles); }
+        break;
+      }
+      if (shape == 0) { launch_p8p<false>(p, one, pgrid, m_tiles, n_tiles, s); break; }
+      if (shape == 1) { launch_p8p<true>(p, one, pgrid, m_tiles, n_tiles, s); break; }
+#endif
+      launch_p8p<kP8Narrow>(p, one, pgrid, m_tiles, n_tiles, s);
     }
   }
 #undef ASV_P8

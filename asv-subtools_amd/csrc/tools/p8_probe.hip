@@ -3,6 +3,10 @@
 // reference on sampled entries; timing in interleaved rounds inside one process (cdna_hip_programming.md 5.4 rules 13 / 24 / 25:
 // uniform random operands in [-1, 1), medians over rounds).  Developer tool, not part of libasv_amd.so's ABI.
 //     p8_probe [rows cin cout ntaps iters rounds]
+// Matrix-instruction shape of the persistent kernel (variants 60 / 61 = 32x32x16 / 16x16x32, 62 / 63 the same with K-loop stamps): the
+// production phase pattern itself on random bf16 - 16 wide or 32 narrow instructions per cluster at priority 1, the partner wave
+// issuing 12 / 8 ds_read_b128 and 4 DMA pieces - timed by wall clock in the interleaved rounds and by s_memtime around the first
+// tile's K loop, with the outputs of the two shapes compared bit for bit.
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -114,6 +118,38 @@ int main(int argc, char **argv) {
       printf("p8 four-phase form vs big3: %zu differing values\n", d4);
     }
   }
+  // ---- the two matrix-instruction shapes of the persistent kernel: equal bits, K-loop ticks of the first tile of every workgroup
+  {
+    std::vector<uint16_t> hs0((size_t)rows * cout_pad), hs1((size_t)rows * cout_pad);
+    CK(hipMemset(y0, 0x77, (size_t)rows * cout_pad * 2)); CK(hipMemset(y1, 0x99, (size_t)rows * cout_pad * 2));
+    p.y = y0; if (launch_tdnn_p8_variant(p, 60, 0)) { printf("p8 persistent 32x32x16 launch failed: %s\n", asv_last_error()); return 1; }
+    p.y = y1; if (launch_tdnn_p8_variant(p, 61, 0)) { printf("p8 persistent 16x16x32 launch failed: %s\n", asv_last_error()); return 1; }
+    CK(hipMemcpy(hs0.data(), y0, hs0.size() * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(hs1.data(), y1, hs1.size() * 2, hipMemcpyDeviceToHost));
+    size_t dn = 0, dw = 0;
+    for (int r = 0; r < rows; ++r) for (int c = 0; c < p.cout_store; ++c) { const size_t i = (size_t)r * cout_pad + c; dn += hs0[i] != hs1[i]; dw += hs0[i] != h0[i]; }
+    printf("p8 persistent 16x16x32 vs 32x32x16: %zu differing values; 32x32x16 vs big3: %zu\n", dn, dw);
+    const int n_wg = std::min((rows / 256) * (cout_pad / 256), 256);
+    unsigned long long *dbg; CK(hipMalloc(&dbg, (size_t)256 * 64));
+    p.partial = reinterpret_cast<float *>(dbg); p.y = y1;
+    for (int shape = 0; shape < 2; ++shape) {
+      double lo = 1e30, hi = 0;
+      std::vector<unsigned long long> h((size_t)256 * 8);
+      for (int rep = 0; rep < 5; ++rep) {
+        CK(hipMemset(dbg, 0, (size_t)256 * 64));
+        if (launch_tdnn_p8_variant(p, 62 + shape, 0)) { printf("stamp launch failed: %s\n", asv_last_error()); return 1; }
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
+        double k = 0;
+        for (int w = 0; w < n_wg; ++w) k += (double)(h[w * 8 + 2] - h[w * 8 + 1]);
+        k /= n_wg;
+        if (rep > 0) { lo = std::min(lo, k); hi = std::max(hi, k); }
+      }
+      printf("p8 persistent %s: K loop of the first tile %.0f - %.0f s_memtime ticks (%.0f - %.0f per K-tile; mean over %d workgroups, 4 launches)\n",
+             shape ? "16x16x32" : "32x32x16", lo, hi, lo / ((cin / 64) * ntaps), hi / ((cin / 64) * ntaps), n_wg);
+    }
+    p.partial = nullptr;
+    CK(hipFree(dbg));
+  }
   // ---- phase stamps of the production kernel (variant 7): prologue | K loop | epilogue, cycles of wave 0, mean over the workgroups
   {
     const int n_wg = (rows / 256) * (cout_pad / 256);
@@ -132,7 +168,7 @@ int main(int argc, char **argv) {
   }
   // ---- timing: interleaved rounds
   struct Var { const char *name; int kind, variant; };
-  const Var vars[] = {{"big3 128x256 (2 WG/CU)", 0, 0}, {"p8 persistent (production)", 1, 0}, {"p8 one tile per workgroup", 1, 50}, {"p8 four-phase, one tile", 1, 40},
+  const Var vars[] = {{"big3 128x256 (2 WG/CU)", 0, 0}, {"p8 persistent (production)", 1, 0}, {"p8 persistent 32x32x16", 1, 60}, {"p8 persistent 16x16x32", 1, 61}, {"p8 one tile per workgroup", 1, 50}, {"p8 four-phase, one tile", 1, 40},
                       {"p8 one tile, no stagger", 1, 1}, {"p8 one tile, without setprio", 1, 2}, {"p8 one tile, skeleton", 1, 4}};
   const int nv = sizeof(vars) / sizeof(vars[0]);
   std::vector<std::vector<float>> us(nv);
